@@ -62,8 +62,9 @@ def parse():
     ap.add_argument("--no-wgrad-arena", action="store_true",
                     help="a fresh zero-filled tensor per weight gradient (default: one arena, zeroed once per step)")
     ap.add_argument("--wgrad-stream", action="store_true",
-                    help="weight-gradient kernels on a side stream = a parallel branch of the graph (measured: 1520 vs 1571 "
-                         "samples/s on the main stream -- the branch competes for the CUs it was meant to fill; off by default)")
+                    help="weight-gradient kernels on a side stream in eager steps; a captured step keeps them on the capturing "
+                         "stream (measured: 1520 vs 1571 samples/s on the main stream -- the branch competes for the CUs it was "
+                         "meant to fill; off by default)")
     ap.add_argument("--aten-profile", action="store_true", help="development: after the warm-up, one eager step under "
                     "torch.profiler; prints the framework (aten) operators that still launch kernels, by input shapes and "
                     "innermost package frame, to stderr")
@@ -77,7 +78,38 @@ def parse():
                     "box the heuristics picked a 244 us forward solver where the search finds a 48 us one (0.54 vs 0.23 ms per "
                     "step).  (A same-box A/B cannot show this: the first run's search result stays in the library's user "
                     "database and the run without the search finds it there.)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy: the loss, the "
+                         "logits and a fixed sample of the updated parameters (and of their gradients) in float32, the "
+                         "sample's positions in float64")
     return ap.parse_args()
+
+
+DUMP_SAMPLE = 2 << 20                                # positions per sampled array: about 32 MB written in all
+
+
+def dump_outputs(out_dir, loss, logits, model):
+    """The arrays the timed step hands its caller, for output-for-output comparison of two builds: the loss, the logits and
+    the updated parameters (and their gradients, where the step leaves them on the parameters).  The parameters are too
+    large to write whole; the same seeded sample of positions (over all of them, flattened in named_parameters() order) is
+    written every time."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    params = [p for _, p in model.named_parameters()]
+    total = sum(p.numel() for p in params)
+    g = torch.Generator().manual_seed(0)
+    idx = torch.randperm(total, generator=g)[:DUMP_SAMPLE].sort().values if total > DUMP_SAMPLE else torch.arange(total)
+    idx = idx.to(params[0].device)
+
+    def sample(ts):
+        return torch.cat([t.detach().float().reshape(-1) for t in ts])[idx].cpu().numpy()
+
+    arrays = {"loss": loss.detach().float().reshape(1).cpu().numpy(), "logits": logits.detach().float().cpu().numpy(),
+              "params_sample": sample(params), "params_sample_index": idx.cpu().numpy().astype(np.float64)}
+    if all(p.grad is not None for p in params):
+        arrays["grads_sample"] = sample([p.grad for p in params])
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def cpu_baseline(batch=2, size=224):
@@ -326,6 +358,9 @@ def main():
         phased = PhasedGrads(model, wire_dtype=comm or torch.float32)
         model.mamba_feature_extrac.cut_after = a.dp_cut
 
+    last = {}                                        # the logits of the latest step (under a graph: its static output),
+                                                     # detached: holding the autograd graph would carry its nodes into the next step
+
     def forward_loss():
         buckets.zero_grad()
         if arena is not None:
@@ -333,6 +368,7 @@ def main():
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=use_bf16):
             out = model(xa, xb)
             loss = crit(out.float(), lab)
+        last["logits"] = out.detach()
         return loss
 
     def fwd_bwd():
@@ -539,6 +575,10 @@ def main():
     fence()
     dt = time.perf_counter() - t0
     _lib.set_timer(None)
+    if a.dump_outputs and rank == 0:                 # before the eager kernel-timing steps below change the model again
+        join_wgrad_stream()
+        dump_outputs(a.dump_outputs, loss, last["logits"], model)
+        torch.cuda.synchronize()
     if graph is not None and not a.no_kernel_timer:
         # per-kernel HIP-event timing cannot live inside a captured graph: the same step is run eagerly, with
         # events around every hand-written launch, right after the timed region (not part of `value`)

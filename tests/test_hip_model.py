@@ -581,7 +581,8 @@ def test_model_tiny_fp32_every_gradient_tensor_matches_the_oracle():
 
 @pytest.mark.parametrize("B,find,wstream", [
     (16, False, False), (32, True, False),
-    (32, True, True),       # bench.py --wgrad-stream: weight-gradient kernels on a side stream = a parallel branch of the graph
+    (32, True, True),       # bench.py --wgrad-stream: weight-gradient kernels on a side stream in the eager step; the captured
+                            # step keeps them on the capturing stream (proj.wgrad_mfma)
     (32, True, "arena"),    # bench.py's default: weight gradients accumulate into one arena that is zeroed once per step,
                             # LayerNorm / bias column sums folded by one launch at the join (xfmamba_amd/deferred.py)
     # (until round 5 an expected failure: with a merged batch of 8 the convolution library's weight-gradient solver for the

@@ -45,10 +45,12 @@ _WGRAD = os.environ.get("XFM_WGRAD", "1") == "1"
 # A weight gradient has no consumer before the optimizer, and the token-contracting kernel runs one workgroup per CU (its
 # atomic tail sets the slice count): next to it the CUs have room for the element-wise / LayerNorm / scan kernels of the
 # main backward chain.  With ``wgrad_stream(True)`` the launches whose result IS the returned gradient go to one side
-# stream (forked from the current stream, so they are captured into the step's hipGraph as a parallel branch) and the
-# caller joins it -- ``join_wgrad_stream()`` -- before anything reads ``.grad`` (FusedAdam.step and GradBuckets do).  Off by
-# default: code that reads gradients straight after ``backward()`` must not need to know about it -- and measured on the
-# XFMamba-T step it LOSES (1520 vs 1571 samples/s: the branch takes CUs from kernels that were already filling them).
+# stream (forked from the current stream) and the caller joins it -- ``join_wgrad_stream()`` -- before anything reads
+# ``.grad`` (FusedAdam.step and GradBuckets do).  Only eagerly: while the current stream is being captured the launches
+# stay on it, because a hipGraph whose capture forks to a second stream and joins it again ends the process with a host
+# segmentation fault in hipGraphLaunch on replay (ROCm 7).  Off by default: code that reads gradients straight after
+# ``backward()`` must not need to know about it -- and measured on the XFMamba-T step it LOSES (1520 vs 1571 samples/s:
+# the branch takes CUs from kernels that were already filling them).
 _SIDE = {"on": False, "stream": None, "pending": False}
 
 
@@ -194,7 +196,7 @@ def wgrad_mfma(a: torch.Tensor, a_planes: bool, b: torch.Tensor, b_planes: bool,
             _lib.check(lib.xfm_wgrad(a.data_ptr(), b.data_ptr(), dw.data_ptr(), M, N, Bt, L, a_bs, b_bs, int(a_planes),
                                      int(b_planes), _lib.stream_ptr()), "wgrad")
 
-    if deferred and _SIDE["on"]:
+    if deferred and _SIDE["on"] and not torch.cuda.is_current_stream_capturing():
         if _SIDE["stream"] is None:
             _SIDE["stream"] = torch.cuda.Stream(device=a.device)
         side = _SIDE["stream"]
