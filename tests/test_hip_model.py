@@ -6,7 +6,7 @@ import torch
 
 from oracle.golden_inputs import g5_inputs
 from oracle import xfm_oracle as O
-from tests.helpers import assert_close, load_json, load_npz
+from tests.helpers import MODEL_CFGS, _model_with_synth_weights, _oracle_autocast_grads, assert_close, load_json, load_npz
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -225,22 +225,6 @@ def test_vss_stage_tokens_stream_drop_path_matches_planes():
         assert_close(gt[k], gp[k], 2e-3, 2e-4 * float(gp[k].abs().max()) + 1e-8, f"d{k}")
 
 
-# BASELINE.json model sizes: (golden tag, type, ctor kwargs, image size, batch) -- net_fusionmamba.py:150-159
-MODEL_CFGS = {
-    "tiny": ("g5", "tiny", {}, 224, 2),                                   # configs[0]/[1]
-    "small": ("g5s", "small", {}, 224, 2),                                # configs[2]
-    "base384": ("g5b", "base", dict(hidden_dim=1024), 384, 1),            # configs[3]
-}
-
-
-def _model_with_synth_weights(ty="tiny", kw=None):
-    from xfmamba_amd.net_fusionmamba import TwoViewXFMambaTop
-    shapes = load_json("g5_state_shapes.json")[ty]
-    m = TwoViewXFMambaTop(in_channels=1, outputs=2, type=ty, **(kw or {}))
-    m.load_state_dict(O.synth_state_dict(shapes, seed=0), strict=True)
-    return m.to(DEV)
-
-
 def _tiny_with_synth_weights():
     return _model_with_synth_weights("tiny")
 
@@ -409,17 +393,6 @@ def test_model_tiny_bf16_at_the_bench_batch_matches_oracle_samples():
     assert torch.isfinite(logits).all() and float(logits.std(0).min()) > 0
 
 
-def _oracle_autocast_grads(ty_tag, sd, xa, xb, lab):
-    """Gradients of the CPU oracle under bf16 autocast (same GEMM precision as the bench configuration, fp32 scan): the
-    yardstick for what bf16 arithmetic itself does to the gradients."""
-    from oracle import c_scan
-    leaves = {k: v.clone().requires_grad_(v.is_floating_point() and "running_" not in k) for k, v in sd.items()}
-    with torch.autocast("cpu", dtype=torch.bfloat16):
-        out = O.xfmamba_top_ref(leaves, xa, xb, True, c_scan.selective_scan_c)
-    torch.nn.functional.cross_entropy(out.float(), lab).backward()
-    return {k: v.grad for k, v in leaves.items() if v.requires_grad and v.grad is not None}
-
-
 @pytest.mark.parametrize("cfg", ["tiny", "small", "base384"])
 def test_model_bf16_autocast_gradients_track_the_oracle(cfg):
     """bf16 GRADIENT parity of XFMamba-T / -S (batch 2) and -B at 384^2 (batch 1) in the bench arithmetic
@@ -450,9 +423,7 @@ def test_model_bf16_autocast_gradients_track_the_oracle(cfg):
         eh = abs(float(gh.double().norm()) - rn) / (rn + 1e-12)
         eo = abs(float(go.double().norm()) - rn) / (rn + 1e-12)
         # norm error of the HIP path within 1.5x the oracle's own bf16 error, with a floor of 5e-2 for small tensors
-        # (1e-1 for the 27-block-deep stage of XFMamba-B at batch 1: the oracle's scan runs in fp32 on fp32 operands, the
-        #  HIP path's on bf16 operands, so the yardstick underestimates the sums behind A_logs / Ds / dt_projs_bias)
-        assert eh <= 1.5 * eo + (1e-1 if cfg == "base384" else 5e-2), (k, eh, eo)
+        assert eh <= 1.5 * eo + 5e-2, (k, eh, eo)
         worst = max(worst, (eh, k))
         if rn > 1e-6 * max(ref_norm.values()):
             cos = float(torch.nn.functional.cosine_similarity(gh.flatten().double(), go.flatten().double(), dim=0))
