@@ -430,7 +430,7 @@ typedef struct {
     const float *D, *delta_bias; /* (4*d_inner) */
     void *y;               /* (batch, d_inner, H*W) */
     float *chk;            /* (batch, 4, d_inner, n_chunks, dstate) fp32 chunk states written by fwd, read by
-                              bwd; may be NULL iff xfm_ss2d_plan() says n_chunks == 1 */
+                              bwd, n_chunks = xfm_ss2d_chk_chunks(); may be NULL iff that is 1 */
     /* backward */
     const void *dy;        /* (batch, d_inner, H*W) out_dtype */
     void *dx;              /* (batch, d_inner, H*W) in_dtype */
@@ -445,7 +445,7 @@ typedef struct {
     int dt_rank_p;         /* xfm_ss2d_dtfused_rank(...) */
     int bc_f32;            /* 1: Bs32 / Cs32 below hold the B / C rows as fp32 too (xfm_ss2d_route_split_bc32); forward AND backward of
                             * such a call are served by csrc/ss2d_w.hpp (xfm_ss2d_bc_f32() says for which shapes), whose
-                            * backward reads the fp32 rows; chk then holds one state per 8-position chunk (xfm_ss2d_plan) */
+                            * backward reads the fp32 rows; chk then holds one state per 8-position chunk (xfm_ss2d_chk_chunks) */
     const float *Bs32, *Cs32;   /* (batch, 4, dstate, H*W) fp32, per-route order; read only when bc_f32 */
 } xfm_ss2d_params_t;
 
@@ -466,8 +466,12 @@ int xfm_ss2d_dtfused_rank(int batch, int d_inner, int H, int W, int dstate, int 
  * routes, rows already in per-route order (xfm_ss2d_route_split); 16-bit dtypes, L % 8 == 0, Rp 6 or 12. */
 int xfm_ss2d_xr_rows(const void *xr, void *xrt, long long B4, int R, int Rp, int L, int dtype, void *stream);
 
-/* The chunking (and so the size of chk) depends on the I/O dtype: 16-byte vectors per lane where rows allow. */
+/* The chunking depends on the I/O dtype: 16-byte vectors per lane where rows allow.  n_chunks covers every kernel family a call
+ * of this shape can take; xfm_ss2d_chk_chunks is exact for one call. */
 int xfm_ss2d_plan(int batch, int d_inner, int H, int W, int dstate, int in_dtype, xfm_scan_plan_t *plan);
+/* n_chunks of chk for the call p describes (every field but the pointers filled: the kernel family that will serve it depends
+ * on the shape, dtypes, delta_softplus, dt_rank_p and bc_f32), or a negative XFM_E* code when no kernel serves it. */
+int xfm_ss2d_chk_chunks(const xfm_ss2d_params_t *p);
 int xfm_ss2d_fwd(const xfm_ss2d_params_t *p, void *stream);
 int xfm_ss2d_bwd(const xfm_ss2d_params_t *p, void *stream);
 /* The same backward with a caller-owned scratch buffer.  Where the kernel family supports it (the wide-map kernels of

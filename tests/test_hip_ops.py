@@ -670,6 +670,15 @@ def test_layernorm_rows_with_conv_bias_and_bf16_input(C, xdt, hdt):
         assert_close(a.grad.float().cpu(), r.grad, tol, 2 * tol * float(r.grad.abs().max()), name)
 
 
+def _ss2d_plan_chunks(B, D, H, W, N, dt):
+    """n_chunks of xfm_ss2d_plan, 0 when the plan needs no checkpoint buffer."""
+    import ctypes
+    from xfmamba_amd import _lib
+    plan = _lib.ScanPlan()
+    _lib.check(_lib.lib().xfm_ss2d_plan(B, D, H, W, N, _lib.dtype_code(dt), ctypes.byref(plan)), "ss2d_plan")
+    return plan.n_chunks if plan.n_chunks > 1 else 0
+
+
 # (the 48 x 48 / 24 x 24 shapes at XFMamba-B's channel counts fill every CU with two workgroups at batch 2: the configuration in
 #  which a 16-byte buffer store's data registers were overwritten behind it -- csrc/ss2d_w.hpp, w_st16)
 # (56 x 56 and 24 x 24 run their last chunk row one position per lane -- csrc/ss2d_w.hpp, WTail1 --: one sample, an odd batch, the
@@ -703,6 +712,17 @@ def test_ss2d_proj_core_matches_operator_chain(shape, dt):
             r = to_route_order(t[1].view(B, K, C2, L), H, W)
             dts = torch.matmul(t[2].to(dt), r[:, :, :R])
             y = ss2d_core_fn(t[0], dts, t[3], r[:, :, R:R + N].contiguous(), r[:, :, R + N:].contiguous(), t[4], t[5], H, W)
+        # the checkpoint buffer the node saved is sized for the kernel family that ran: on the wide maps one state per 512-position
+        # chunk row (ss2d_l3.hip: mode 1 here, and mode 2 without fp32 B / C rows), one per lane with them (ss2d_w.hpp: the default
+        # bf16 mode-2 call); the plan's chunking on every other shape and dtype
+        saved = y.grad_fn.saved_tensors
+        chk, b32 = (saved[9], saved[13]) if fused else (saved[7], None)
+        rows = 0 if chk is None else chk.shape[3]
+        if dt == torch.bfloat16 and N == 1 and H == W and H in (56, 48, 28, 24):
+            assert b32 is not None or not fused or H != 56
+            assert rows == (L + 511) // 512 * (64 if b32 is not None else 1), (fused, rows)
+        else:
+            assert b32 is None and rows == _ss2d_plan_chunks(B, D, H, W, N, dt), rows
         y.backward(gy.to(DEV))
         outs.append([y.detach()] + [v.grad for v in t])
     tol = 1e-4 if dt == torch.float32 else 1e-2

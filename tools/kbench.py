@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Micro-benchmark of the hand-written kernels at the BASELINE shapes (XFMamba-T, batch 32 x 2 views).
 
-    python tools/kbench.py [--only ss2d] [--force kind,lg,items,pli]   (XFM_SS2D_FORCE plan override)
+    python tools/kbench.py [--only ss2d]
 
 Prints per-kernel time (HIP events on the launch stream, median of repeats), algorithmic GB/s
 (SURVEY.md 8(d) byte counts) and the fraction of the 8 TB/s HBM peak.
@@ -50,12 +50,9 @@ def timeit(fn, reps=20, warm=3):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="")
-    ap.add_argument("--force", default=None)
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--batch", type=int, default=64)
     a = ap.parse_args()
-    if a.force:
-        os.environ["XFM_SS2D_FORCE"] = a.force
     from xfmamba_amd import _lib
     from xfmamba_amd.ss2d import SS2DCoreHip
     from xfmamba_amd.dwconv import DWConv3x3SiLUHip

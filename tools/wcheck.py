@@ -4,6 +4,7 @@ same seeded inputs -- y and every gradient; shapes on the command line as B,D,HW
 import os
 import subprocess
 import sys
+import tempfile
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
@@ -30,11 +31,14 @@ def run(shape):
 def main():
     shapes = [tuple(int(v) for v in s.split(",")) for s in sys.argv[1:] if "," in s] or [(2, 512, 48, 16), (2, 1024, 24, 32)]
     if "--child" in sys.argv:
-        torch.save([run(s) for s in shapes], "/tmp/wcheck_l3.pt")
+        torch.save([run(s) for s in shapes], sys.argv[sys.argv.index("--child") + 1])
         return
     env = dict(os.environ, XFM_SS2D_W="0")
-    subprocess.run([sys.executable, os.path.abspath(__file__), "--child"] + [",".join(map(str, s)) for s in shapes], env=env, check=True)
-    ref = torch.load("/tmp/wcheck_l3.pt")
+    with tempfile.TemporaryDirectory() as tmp:
+        out = os.path.join(tmp, "wcheck_l3.pt")
+        subprocess.run([sys.executable, os.path.abspath(__file__), "--child", out] + [",".join(map(str, s)) for s in shapes], env=env,
+                       check=True)
+        ref = torch.load(out)
     for s, r in zip(shapes, ref):
         got = run(s)
         for name, a, b in zip(("y", "dx", "dxw", "ddtw", "dA", "dD", "dbias"), got, r):

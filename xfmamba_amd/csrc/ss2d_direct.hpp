@@ -462,14 +462,11 @@ __global__ void __launch_bounds__(256) ss2d_fwd_direct_kernel(const SS2DArgs a) 
         const int d0 = tile * G;
         const int64_t po = ((int64_t)b * p.d_inner + d0) * L;
         __syncthreads();
-        if (!(a.dbg & 2))
-            planes_load_nt<Tin, Tin>(xN, xT, (const Tin *)p.x + po, G, L, a.PSZ, H, W, a.magicW,
-                                     (int64_t)p.batch * p.d_inner * L - po, threadIdx.x, 256);
+        planes_load_nt<Tin, Tin>(xN, xT, (const Tin *)p.x + po, G, L, a.PSZ, H, W, a.magicW,
+                                 (int64_t)p.batch * p.d_inner * L - po, threadIdx.x, 256);
         __syncthreads();
-        if (!(a.dbg & 1))
-            sweep_fwd_d<Tin, N1>(a, k, rev, carry, bc, (col ? xT : xN) + g * a.PSZ, ypl + g * a.PSZ, b, d0, g, i, lane, pf, tile0, n_tiles, it);
+        sweep_fwd_d<Tin, N1>(a, k, rev, carry, bc, (col ? xT : xN) + g * a.PSZ, ypl + g * a.PSZ, b, d0, g, i, lane, pf, tile0, n_tiles, it);
         __syncthreads();
-        if (a.dbg & 4) continue;
         const size_t ws = a.lds_floats_per_wave;
         const float *Y0 = wbase - (size_t)wave * ws, *Y1 = Y0 + ws, *Y2 = Y1 + ws, *Y3 = Y2 + ws;
         Tout *yo = (Tout *)p.y + po;
@@ -515,17 +512,13 @@ __global__ void __launch_bounds__(256) ss2d_bwd_direct_kernel(const SS2DArgs a) 
         const int64_t po = ((int64_t)b * p.d_inner + d0) * L;
         const int64_t room = (int64_t)p.batch * p.d_inner * L - po;
         __syncthreads();
-        if (!(a.dbg & 2)) {
-            planes_load_nt<Tin, Tin>(xN, xT, (const Tin *)p.x + po, G, L, a.PSZ, H, W, a.magicW, room, threadIdx.x, 256);
-            planes_load_nt<Tout, Tin>(gN, gT, (const Tout *)p.dy + po, G, L, a.PSZ, H, W, a.magicW, room, threadIdx.x, 256);
-        }
+        planes_load_nt<Tin, Tin>(xN, xT, (const Tin *)p.x + po, G, L, a.PSZ, H, W, a.magicW, room, threadIdx.x, 256);
+        planes_load_nt<Tout, Tin>(gN, gT, (const Tout *)p.dy + po, G, L, a.PSZ, H, W, a.magicW, room, threadIdx.x, 256);
         for (int e = threadIdx.x; e < 2 * GP; e += 256) dxN[e] = 0.f;
         __syncthreads();
-        if (!(a.dbg & 1))
-            sweep_bwd_d<Tin, N1>(a, k, rev, carryE, bc, (col ? xT : xN) + g * a.PSZ, (col ? gT : gN) + g * a.PSZ,
-                                 (col ? dxT : dxN) + g * a.PSZ, b, d0, g, i, lane, acc, pf, tile0, n_tiles, it);
+        sweep_bwd_d<Tin, N1>(a, k, rev, carryE, bc, (col ? xT : xN) + g * a.PSZ, (col ? gT : gN) + g * a.PSZ,
+                             (col ? dxT : dxN) + g * a.PSZ, b, d0, g, i, lane, acc, pf, tile0, n_tiles, it);
         __syncthreads();
-        if (a.dbg & 4) continue;
         Tin *dxo = (Tin *)p.dx + po;
         for (int g2 = 0; g2 < G; ++g2)
             for (int e = threadIdx.x; e < L; e += 256) {

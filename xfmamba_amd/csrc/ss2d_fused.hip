@@ -1,7 +1,4 @@
 // ss2d_fused.hip -- host side of the fused SS2D core (planning, launch, C ABI).  Kernels: ss2d_kernels.hpp.
-#include <cstdio>
-#include <cstdlib>
-
 #include "ss2d_kernels.hpp"
 
 namespace xfm {
@@ -11,32 +8,28 @@ static const size_t kLdsPerCU = 160 * 1024;
 static inline size_t up4(size_t v) { return (v + 3) & ~(size_t)3; }
 
 // One decomposition serves forward and backward (they share the chunk-state layout `chk`).
-static int plan_ss2d(int batch, int D, int H, int W, int N, int in_dtype, Plan2 *out) {
+int plan_ss2d(int batch, int D, int H, int W, int N, int in_dtype, Plan2 *out) {
     if (batch <= 0 || D <= 0 || H <= 0 || W <= 0 || N <= 0) return XFM_EINVAL;
     if (N > 256 || (int64_t)H * W >= 65536) return XFM_ELIMIT;
     const int L = H * W;
     const size_t PSZ = up4((size_t)H * (W | 1));
-    // tuning hook (tools/kbench.py): XFM_SS2D_FORCE="kind,lg,items,pli" restricts the search
-    int f_kind = -1, f_lg = -1, f_items = -1, f_pli = -1;
-    if (const char *env = getenv("XFM_SS2D_FORCE")) sscanf(env, "%d,%d,%d,%d", &f_kind, &f_lg, &f_items, &f_pli);
     out->psz = (int)PSZ;
     const int sz = in_dtype == XFM_F32 ? 4 : 2;
     // ---- lean variant for d_state == 1 (ss2d_lean.hpp): rows are whole vectors, PPT planes per tile
-    if ((f_kind < 0 || f_kind == 3) && N == 1 && L % 4 == 0 && W > 1) {
+    if (N == 1 && L % 4 == 0 && W > 1) {
         const int c = (sz == 2 && L % 8 == 0) ? 8 : 4;
         const int nseg = (L + 64 * c - 1) / (64 * c);
         int ppt = 1;
         for (int q = 1; q <= D; ++q)
             if (D % q == 0 && (int64_t)q * L <= 3200) ppt = q;
-        if (f_lg > 0 && D % f_lg == 0) ppt = f_lg;                     // (tuning hook: "lg" field = planes per tile)
         const size_t PL = (size_t)ppt * L;
         const size_t fwd_blk = 6 * PL * sz;
         // registers win for short rows; from ~4 chunks on the LDS accumulators are faster (measured, stage 0: 473 vs 563 us)
         const bool has_reg = nseg <= 2;
         // one-plane tiles beyond the staging span of the regular variants (96 x 96, XFMamba-B at 384^2): the BIG
         // variants -- 16-bit I/O only, accumulators of all 18 chunk rows in registers (ss2d_lean.hpp)
-        const bool big = PL > 4096 && ppt == 1 && c == 8 && nseg == 18 && L <= 9216 && f_lg <= 0;
-        const int reg_nseg = big ? 18 : ((has_reg && !getenv("XFM_SS2D_LDSACC")) ? nseg : 0);
+        const bool big = PL > 4096 && ppt == 1 && c == 8 && nseg == 18 && L <= 9216;
+        const int reg_nseg = big ? 18 : (has_reg ? nseg : 0);
         const size_t bwd_blk = 8 * PL * sz + (reg_nseg ? 0 : (size_t)8 * L * sizeof(float));
         // (PL <= 4096: the staging registers of the lean kernels cover a tile of 256 threads x 16 elements)
         if (fwd_blk <= kLdsPerCU && bwd_blk <= kLdsPerCU && (PL <= 4096 || big)) {
@@ -58,7 +51,6 @@ static int plan_ss2d(int batch, int D, int H, int W, int N, int in_dtype, Plan2 
                 int pli = (int)((int64_t)batch * tiles_pb / ((int64_t)256 * resident * 2));
                 if (pli < 1) pli = 1;
                 if (pli > tiles_pb) pli = tiles_pb;
-                if (f_pli > 0) pli = std::min(f_pli, tiles_pb);
                 while (tiles_pb % pli) --pli;
                 return pli;
             };
@@ -67,14 +59,12 @@ static int plan_ss2d(int batch, int D, int H, int W, int N, int in_dtype, Plan2 
             return XFM_OK;
         }
     }
-    if (f_kind == 3) return XFM_ELIMIT;
     // ---- direct variant: chunk = one 16-byte vector, planes in both layouts (ss2d_direct.hpp)
-    if ((f_kind < 0 || f_kind == 2) && ((int64_t)L * sz) % 4 == 0) {
+    if (((int64_t)L * sz) % 4 == 0) {
         const int c = 16 / sz;
         const int chunks = (L + c - 1) / c;
         int lg = 0;
         while (lg < 6 && (1 << lg) < chunks) ++lg;
-        if (f_lg >= 0) lg = f_lg;
         while (lg < 6 && (D % (64 >> lg) || (64 >> lg) * N > 2048)) ++lg;
         const int G = 64 >> lg;
         if (D % G == 0 && G * N <= 2048) {
@@ -102,25 +92,20 @@ static int plan_ss2d(int batch, int D, int H, int W, int N, int in_dtype, Plan2 
                 int pli = (int)((int64_t)batch * tiles_pb / ((int64_t)256 * resident * 2));
                 if (pli < 1) pli = 1;
                 if (pli > tiles_pb) pli = tiles_pb;
-                if (f_pli > 0) pli = std::min(f_pli, tiles_pb);
                 while (tiles_pb % pli) --pli;
                 out->pli = pli;
                 return XFM_OK;
             }
         }
     }
-    if (f_kind == 2) return XFM_ELIMIT;
     for (int kind = 1; kind >= 0; --kind) {
-        if (f_kind >= 0 && kind != f_kind) continue;
         double best = 1e300;
         bool found = false;
         for (int lg = 0; lg <= 6; ++lg) {
             const int G = 64 >> lg;
             if (D % G) continue;
             if (G * N > 2048) continue;
-            if (f_lg >= 0 && lg != f_lg) continue;
             for (int c : kItems2) {
-                if (f_items >= 0 && c != f_items) continue;
                 const int SL = c << lg;
                 const int nseg = (L + SL - 1) / SL;
                 const size_t bcf = (N > 1 && nseg == 1 && (size_t)2 * N * L <= 4096) ? up4((size_t)2 * N * L) : 0;
@@ -178,7 +163,6 @@ static int plan_ss2d(int batch, int D, int H, int W, int N, int in_dtype, Plan2 
                 int pli = (int)((int64_t)batch * tiles_pb / ((int64_t)256 * resident * 2));
                 if (pli < 1) pli = 1;
                 if (pli > tiles_pb) pli = tiles_pb;
-                if (f_pli > 0) pli = std::min(f_pli, tiles_pb);
                 while (tiles_pb % pli) --pli;                              // equal work per workgroup
                 out->pli = pli;
             }
@@ -225,7 +209,6 @@ int ss2d_launch_lean(const void *fn, const SS2DArgs &a, const Plan2 &pl, bool bw
     la.magicW = a.magicW;
     la.magicL = (uint32_t)((0x100000000ull + la.L - 1) / la.L);
     la.magicH = (uint32_t)((0x100000000ull + la.H - 1) / la.H);
-    la.dbg = a.dbg;
     const size_t lds = bwd ? pl.lds_bwd_block : pl.lds_fwd_block;
     const unsigned grid = (unsigned)((int64_t)p.batch * (p.d_inner / pl.ppt / la.pli));
     if (lds > 64 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -238,41 +221,19 @@ int ss2d_launch_lean(const void *fn, const SS2DArgs &a, const Plan2 &pl, bool bw
     return check_launch();
 }
 
-int ss2d_l3_run(const xfm_ss2d_params_t *p, bool bwd, hipStream_t s, float *ws, size_t ws_bytes);   // ss2d_l3.hip: wide maps
-size_t ss2d_l3_ws_bytes(const xfm_ss2d_params_t *p);
-int ss2d_l3_nseg(int batch, int D, int H, int W, int N, int in_dtype);
-int ss2d_l3_dtfused_rank(int batch, int D, int H, int W, int N, int R, int in_dtype);
-int ss2d_w_covers(int batch, int D, int H, int W, int N, int in_dtype);                                // ss2d_l3.hip / ss2d_w.hpp
-static bool ss2d_forced() {
-    static const bool f = getenv("XFM_SS2D_FORCE") != nullptr;      // tuning hook, read once per process
-    return f;
-}
-
 static int run2(const xfm_ss2d_params_t *p, bool bwd, void *stream, float *ws = nullptr, size_t ws_bytes = 0) {
     if (!p || !p->x || !p->Bs || !p->Cs || !p->A || !p->D || !p->delta_bias) return XFM_EINVAL;
-    if (p->delta_softplus == 3) {
-        // dt_proj inside the kernel: only the wide-map kernels of ss2d_l3.hip have it (xfm_ss2d_dtfused_rank)
-        if (!p->xrt || !p->dt_w || p->dt_rank_p <= 0) return XFM_EINVAL;
-        if (!bwd && !p->y) return XFM_EINVAL;
-        if (bwd && (!p->dy || !p->dx || !p->ddts || !p->dBs || !p->dCs || !p->dA || !p->dD || !p->ddelta_bias)) return XFM_EINVAL;
-        if (p->out_dtype != XFM_F32) return XFM_EDTYPE;
-        return ss2d_l3_run(p, bwd, (hipStream_t)stream, ws, ws_bytes);
-    }
-    if (!p->dts) return XFM_EINVAL;
+    if (p->delta_softplus == 3 ? (!p->xrt || !p->dt_w || p->dt_rank_p <= 0) : !p->dts) return XFM_EINVAL;
     if (!bwd && !p->y) return XFM_EINVAL;
     if (bwd && (!p->dy || !p->dx || !p->ddts || !p->dBs || !p->dCs || !p->dA || !p->dD || !p->ddelta_bias))
         return XFM_EINVAL;
-    if (p->in_dtype < 0 || p->in_dtype > 2) return XFM_EDTYPE;
-    if (p->out_dtype != XFM_F32) return XFM_EDTYPE;          // the fused core always emits fp32 ("oflex")
-    if (!ss2d_forced()) {
-        const int rc3 = ss2d_l3_run(p, bwd, (hipStream_t)stream, ws, ws_bytes);
-        if (rc3 != XFM_ELIMIT) return rc3;
-    }
-    if (p->bc_f32) return XFM_EINVAL;                        // fp32 B / C rows beside 16-bit planes: ss2d_w.hpp only (xfm_ss2d_bc_f32)
-    Plan2 pl;
-    int rc = plan_ss2d(p->batch, p->d_inner, p->H, p->W, p->dstate, p->in_dtype, &pl);
+    SS2DRoute r;
+    const int rc = ss2d_route(*p, r);
     if (rc) return rc;
-    if (pl.n_chunks > 1 && !p->chk) return XFM_EINVAL;
+    if (r.chk_len > 1 && !p->chk) return XFM_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    if (r.family != SS2D_GENERIC) return ss2d_l3_run(*p, r.family, bwd, s, ws, ws_bytes);
+    const Plan2 &pl = r.plan;
     SS2DArgs a;
     a.p = *p;
     a.lg_lpr = pl.lg;
@@ -284,20 +245,21 @@ static int run2(const xfm_ss2d_params_t *p, bool bwd, void *stream, float *ws = 
     a.kind = pl.kind;
     a.pli = pl.pli;
     a.bc_floats = pl.bc_floats;
-    static const int env_dbg = [] { const char *e = getenv("XFM_SS2D_DBG"); return e ? atoi(e) : 0; }();
-    a.dbg = env_dbg;
-    if (env_dbg) {
-        static int once = 0;
-        if (!once++) fprintf(stderr, "[xfm] ss2d timing switches dbg=%d kind=%d items=%d chunks=%d ppt=%d pli=%d lds=%zu/%zu\n", a.dbg, pl.kind, pl.items, pl.n_chunks, pl.ppt, pl.pli, pl.lds_fwd_block, pl.lds_bwd_block);
-    }
     a.magicW = (uint32_t)((0x100000000ull + p->W - 1) / p->W);
-    hipStream_t s = (hipStream_t)stream;
     switch (p->in_dtype) {
         case XFM_F32: return ss2d_dispatch<float, float>(a, pl, bwd, s);
         case XFM_F16: return ss2d_dispatch<f16_t, float>(a, pl, bwd, s);
         case XFM_BF16: return ss2d_dispatch<bf16_t, float>(a, pl, bwd, s);
     }
     return XFM_EDTYPE;
+}
+
+// a call of this shape in the given step-size mode, for the shape-only queries of the C ABI
+static xfm_ss2d_params_t shape_call(int batch, int d_inner, int H, int W, int dstate, int in_dtype, int mode) {
+    xfm_ss2d_params_t p{};
+    p.batch = batch; p.d_inner = d_inner; p.H = H; p.W = W; p.dstate = dstate;
+    p.in_dtype = in_dtype; p.out_dtype = XFM_F32; p.delta_softplus = mode;
+    return p;
 }
 
 }  // namespace xfm
@@ -311,25 +273,38 @@ int xfm_ss2d_plan(int batch, int d_inner, int H, int W, int dstate, int in_dtype
     if (rc) return rc;
     plan->lanes_per_row = 1 << pl.lg;
     plan->items = pl.items;
-    plan->n_chunks = pl.n_chunks;
-    if (!xfm::ss2d_forced())                       // the wide-map kernels (ss2d_l3.hip) index chk by their own geometry
-        plan->n_chunks = std::max(plan->n_chunks, xfm::ss2d_l3_nseg(batch, d_inner, H, W, dstate, in_dtype));
+    // n_chunks: enough checkpoints for whichever family serves a call of this shape (the wide-map kernels index chk by their
+    // own geometry, ss2d_w.hpp by lane); xfm_ss2d_chk_chunks gives the exact count of one call
+    xfm_ss2d_params_t p = xfm::shape_call(batch, d_inner, H, W, dstate, in_dtype, 2);
+    p.bc_f32 = xfm_ss2d_bc_f32(batch, d_inner, H, W, dstate, in_dtype);
+    xfm::SS2DRoute r;
+    plan->n_chunks = (xfm::ss2d_route(p, r) == XFM_OK) ? std::max(pl.n_chunks, r.chk_len) : pl.n_chunks;
     return XFM_OK;
 }
 int xfm_ss2d_dtfused_rank(int batch, int d_inner, int H, int W, int dstate, int dt_rank, int in_dtype) {
-    if (xfm::ss2d_forced()) return 0;
-    return xfm::ss2d_l3_dtfused_rank(batch, d_inner, H, W, dstate, dt_rank, in_dtype);
+    if (dt_rank <= 0) return 0;
+    xfm_ss2d_params_t p = xfm::shape_call(batch, d_inner, H, W, dstate, in_dtype, 3);
+    p.dt_rank_p = (dt_rank + 1) & ~1;
+    xfm::SS2DRoute r;
+    return (xfm::ss2d_route(p, r) == XFM_OK && r.family == xfm::SS2D_L3) ? p.dt_rank_p : 0;
 }
 int xfm_ss2d_bc_f32(int batch, int d_inner, int H, int W, int dstate, int in_dtype) {
-    if (xfm::ss2d_forced()) return 0;
-    return xfm::ss2d_w_covers(batch, d_inner, H, W, dstate, in_dtype);
+    xfm_ss2d_params_t p = xfm::shape_call(batch, d_inner, H, W, dstate, in_dtype, 2);
+    p.bc_f32 = 1;
+    xfm::SS2DRoute r;
+    return (xfm::ss2d_route(p, r) == XFM_OK && r.family == xfm::SS2D_W) ? 1 : 0;
 }
 int xfm_ss2d_fwd(const xfm_ss2d_params_t *p, void *stream) { return xfm::run2(p, false, stream); }
 int xfm_ss2d_bwd(const xfm_ss2d_params_t *p, void *stream) { return xfm::run2(p, true, stream); }
+int xfm_ss2d_chk_chunks(const xfm_ss2d_params_t *p) {
+    if (!p) return XFM_EINVAL;
+    xfm::SS2DRoute r;
+    const int rc = xfm::ss2d_route(*p, r);
+    return rc ? rc : r.chk_len;
+}
 size_t xfm_ss2d_bwd_ws_bytes(const xfm_ss2d_params_t *p) {
-    if (!p || xfm::ss2d_forced() || getenv("XFM_L3_ATOMICS")) return 0;      // (A/B switch of the tests: read per call)
-    const char *e = getenv("XFM_SS2D_L3");
-    return (e && e[0] == '0') ? 0 : xfm::ss2d_l3_ws_bytes(p);
+    xfm::SS2DRoute r;
+    return (p && xfm::ss2d_route(*p, r) == XFM_OK) ? r.ws_bytes : 0;
 }
 int xfm_ss2d_bwd_ws(const xfm_ss2d_params_t *p, void *workspace, size_t workspace_bytes, void *stream) {
     return xfm::run2(p, true, stream, (float *)workspace, workspace_bytes);

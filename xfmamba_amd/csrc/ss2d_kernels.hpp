@@ -37,7 +37,6 @@ struct SS2DArgs {
     int kind;                    // see above
     int pli;                     // kind 1: consecutive plane tiles handled by one workgroup
     int bc_floats;               // per-wave LDS region holding B,C of the route for all states (0: none)
-    int dbg;                     // timing-only switches (XFM_SS2D_DBG): 1 skip sweeps, 2 skip plane loads, 4 skip merge
     uint32_t magicW;             // ceil(2^32 / W): e / W == __umulhi(e, magicW) for e < 2^16
 };
 
@@ -743,6 +742,19 @@ struct Plan2 {
     size_t lds_fwd_block, lds_bwd_block;         // dynamic LDS bytes per workgroup
     int waves_fwd, waves_bwd;                    // waves per workgroup
 };
+int plan_ss2d(int batch, int D, int H, int W, int N, int in_dtype, Plan2 *out);      // ss2d_fused.hip
+
+// The kernel family that serves a call of the fused core.  Every entry point of the core asks ss2d_route (ss2d_l3.hip) and
+// keeps no rule of its own.
+enum SS2DFamily { SS2D_W, SS2D_L3, SS2D_GENERIC };   // ss2d_w.hpp | the kernels of ss2d_l3.hip | plan_ss2d's kernels
+struct SS2DRoute {
+    SS2DFamily family;
+    int chk_len;                                 // chk entries per (route, channel) row, per state, that the family indexes
+    size_t ws_bytes;                             // backward partial-row workspace the family can use (0: dB / dC by atomics)
+    Plan2 plan;                                  // SS2D_GENERIC: the decomposition
+};
+int ss2d_route(const xfm_ss2d_params_t &p, SS2DRoute &r);              // XFM_OK, or why no family serves the call
+int ss2d_l3_run(const xfm_ss2d_params_t &p, SS2DFamily family, bool bwd, hipStream_t s, float *ws, size_t ws_bytes);
 
 template <typename Tin, typename Tout>
 int ss2d_dispatch(const SS2DArgs &a, const Plan2 &pl, bool bwd, hipStream_t s);

@@ -677,7 +677,7 @@ __device__ __forceinline__ void l3_bwd_plane(const bf16_t *__restrict__ dts_row,
                                              bf16_t *dxq, float *ldsacc, l3f2 (&rB)[L3Geom<HW, RP2>::NACC][4],
                                              l3f2 (&rC)[L3Geom<HW, RP2>::NACC][4], float &dA_acc, float &dD_acc,
                                              float &dbias_acc, const int lane, L3Ops<(MODE == 3 ? 2 * RP2 : 1)> &op,
-                                             const int dbg, const L3Next &nx) {
+                                             const L3Next &nx) {
     using G = L3Geom<HW, RP2>;
     constexpr int L = G::L, NSEG = G::NSEG, NX = MODE == 3 ? 2 * RP2 : 1;
     const float A2 = An * kLog2e;
@@ -733,7 +733,7 @@ __device__ __forceinline__ void l3_bwd_plane(const bf16_t *__restrict__ dts_row,
             const int tpn = spn * G::ROW + ci * 8;
             const bf16_t *drow = (i > 0 || MODE == 3) ? dts_row : dts_row + L;     // (mode 3: the route's rows serve every plane)
             const float *crow = i > 0 ? chk_row : chk_row + NSEG;
-            if ((i > 0 || more_planes) && !(dbg & 16)) {
+            if (i > 0 || more_planes) {
                 const bool ok = !(G::HAS_TAIL && spn == NSEG - 1) || tail_live;
                 if (ok) l3_ops_load<NX>(op, drow, Brow, Crow, tpn);
                 else l3_ops_zero<NX>(op);
@@ -846,7 +846,7 @@ __device__ __forceinline__ void l3_bwd_plane(const bf16_t *__restrict__ dts_row,
             dD2 = __builtin_elementwise_fma(g[q], u[q], dD2);
             db2 += dd[q];
         }
-        if ((!is_tail || tail_live) && !(dbg & 32)) {
+        if (!is_tail || tail_live) {
             *reinterpret_cast<uint4 *>(ddts_row + tp0) = l3_pack<REV>(dd);
             *reinterpret_cast<uint4 *>(dxq + tp0) = l3_pack<REV>(du);      // this route's private dx plane
         }
@@ -947,8 +947,7 @@ __device__ __forceinline__ void l3_bwd_body(const LeanArgs &a, float *smem, cons
     static_assert(PL <= 4096, "tile beyond the staging registers");
     if constexpr (PF) {
         const int64_t po0 = ((int64_t)b * D + (int64_t)tg * a.pli * PPT) * L;
-        if (!(a.dbg & 2))
-            l3_dma_tile<PL>((const bf16_t *)a.x + po0, (const float *)a.dy + po0, l3_lds_addr(xN), l3_lds_addr(graw), wave, lane);
+        l3_dma_tile<PL>((const bf16_t *)a.x + po0, (const float *)a.dy + po0, l3_lds_addr(xN), l3_lds_addr(graw), wave, lane);
     }
 #pragma unroll 1
     for (int it = 0; it < a.pli; ++it) {
@@ -964,13 +963,13 @@ __device__ __forceinline__ void l3_bwd_body(const LeanArgs &a, float *smem, cons
             // tile `it` was sent for during tile it - 1 (or above): wait for this wave's pieces, then for everybody's
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();                           // (also: the previous tile's merge has read the private planes)
-            if (!(a.dbg & 8)) l3_stage_lds<HW, PPT>(xNc, xT, graw, gN, gT, tid);
+            l3_stage_lds<HW, PPT>(xNc, xT, graw, gN, gT, tid);
             nx.x = (const bf16_t *)a.x + po + PL;
             nx.g = (const float *)a.dy + po + PL;
             nx.xdst = l3_lds_addr((it & 1) ? xN : xN1);
             nx.gdst = l3_lds_addr(graw);
             nx.wave = wave;
-            nx.go = it + 1 < a.pli && !(a.dbg & 2);
+            nx.go = it + 1 < a.pli;
         } else if constexpr (HW % 8 == 0) {
             // Register staging in memory order.  (Named scalars, not arrays: hipcc left a uint4 / float4 array as an alloca --
             // 48 bytes of scratch per lane and plane, the vectors stored and re-read around the barrier: 1.9x the algorithmic
@@ -1000,19 +999,15 @@ __device__ __forceinline__ void l3_bwd_body(const LeanArgs &a, float *smem, cons
         } else {
             PlaneRegs<bf16_t, 8, NVX> px;
             PlaneRegs<float, 4, NVG> pg;
-            if (!(a.dbg & 2)) {
-                l3_planes_issue<HW, PPT, bf16_t, 8, NVX>(px, (const bf16_t *)a.x + po, tid);
-                l3_planes_issue<HW, PPT, float, 4, NVG>(pg, (const float *)a.dy + po, tid);
-            }
+            l3_planes_issue<HW, PPT, bf16_t, 8, NVX>(px, (const bf16_t *)a.x + po, tid);
+            l3_planes_issue<HW, PPT, float, 4, NVG>(pg, (const float *)a.dy + po, tid);
             __syncthreads();                           // (the previous tile's merge has read the planes)
-            if (!(a.dbg & 2)) {
-                l3_planes_commit<HW, PPT, bf16_t, 8, NVX>(px, xN, xT, tid);
-                l3_planes_commit<HW, PPT, float, 4, NVG>(pg, gN, gT, tid);
-            }
+            l3_planes_commit<HW, PPT, bf16_t, 8, NVX>(px, xN, xT, tid);
+            l3_planes_commit<HW, PPT, float, 4, NVG>(pg, gN, gT, tid);
         }
         __syncthreads();
 #pragma unroll 1
-        for (int pl = 0; pl < ((a.dbg & 1) ? 0 : PPT); ++pl) {
+        for (int pl = 0; pl < PPT; ++pl) {
             const int d = d0 + pl, row = k * D + d;
             const int64_t ro = (route * D + d) * L;
             const float *chk_row = a.chk + (route * D + d) * NSEG;
@@ -1023,8 +1018,7 @@ __device__ __forceinline__ void l3_bwd_body(const LeanArgs &a, float *smem, cons
             l3_weight_pairs<RP2>(a.dtw, row, wp);
             l3_bwd_plane<HW, REV, MODE, RP2, (PF ? PL : 0)>(MODE == 3 ? drow0 : (const bf16_t *)a.dts + ro, (bf16_t *)a.ddts + ro,
                                                             Brow, Crow, chk_row, more, An, Dr, bias, wp, xq + pl * L, gq + pl * L,
-                                                            dxq + pl * L, ldsacc, rB, rC, dA_acc, dD_acc, dbias_acc, lane, op,
-                                                            a.dbg, nx);
+                                                            dxq + pl * L, ldsacc, rB, rC, dA_acc, dD_acc, dbias_acc, lane, op, nx);
             nx.go = false;
             for (int o = 32; o > 0; o >>= 1) {
                 dA_acc += __shfl_xor(dA_acc, o, 64);
@@ -1038,18 +1032,16 @@ __device__ __forceinline__ void l3_bwd_body(const LeanArgs &a, float *smem, cons
             }
         }
         __syncthreads();
-        if (!(a.dbg & 4)) {
-            int tz2;
-            asm volatile("v_mov_b32 %0, 0" : "=v"(tz2));
-            if constexpr (HW % 8 == 0) {
-                // the sums into the (now free) natural x image in the conflict-free order, then out in memory order
-                l3_merge_store<HW, PPT>(xNc, DX, DX + PL, DX + 2 * PL, DX + 3 * PL, threadIdx.x + tz2);
-                __syncthreads();
-                for (int v = threadIdx.x + tz2; v < PL / 8; v += 256)
-                    *reinterpret_cast<uint4 *>((bf16_t *)a.dx + po + v * 8) = *reinterpret_cast<const uint4 *>(xNc + v * 8);
-            } else {
-                l3_merge_store<HW, PPT>((bf16_t *)a.dx + po, DX, DX + PL, DX + 2 * PL, DX + 3 * PL, threadIdx.x + tz2);
-            }
+        int tz2;
+        asm volatile("v_mov_b32 %0, 0" : "=v"(tz2));
+        if constexpr (HW % 8 == 0) {
+            // the sums into the (now free) natural x image in the conflict-free order, then out in memory order
+            l3_merge_store<HW, PPT>(xNc, DX, DX + PL, DX + 2 * PL, DX + 3 * PL, threadIdx.x + tz2);
+            __syncthreads();
+            for (int v = threadIdx.x + tz2; v < PL / 8; v += 256)
+                *reinterpret_cast<uint4 *>((bf16_t *)a.dx + po + v * 8) = *reinterpret_cast<const uint4 *>(xNc + v * 8);
+        } else {
+            l3_merge_store<HW, PPT>((bf16_t *)a.dx + po, DX, DX + PL, DX + 2 * PL, DX + 3 * PL, threadIdx.x + tz2);
         }
     }
     // ---- flush: registers hold [chunk row][traversal element] of this lane.  Atomics are only fast when a wave
@@ -1121,12 +1113,6 @@ __global__ void __launch_bounds__(256, L3_WPE) ss2d_l3_bwd_kernel(const LeanArgs
 
 namespace xfm {
 
-// fourth-generation kernels (ss2d_w.hpp) for the activated-step-size mode; XFM_SS2D_W=0: the kernels of this file (A/B switch)
-static bool w_enabled() {
-    static const bool on = [] { const char *e = getenv("XFM_SS2D_W"); return !(e && e[0] == '0'); }();
-    return on;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1137,8 +1123,6 @@ static int l3_pli(int batch, int tiles_pb, bool bwd, int fwd_wpe = L3_WPE_FWD) {
     int pli = (int)(((int64_t)batch * tiles_pb + resident - 1) / resident);
     if (pli < 1) pli = 1;
     if (pli > tiles_pb) pli = tiles_pb;
-    static const int env_pli = [] { const char *e = getenv("XFM_L3_PLI"); return e ? atoi(e) : 0; }();   // tuning hook, read once
-    if (env_pli > 0) pli = std::max(1, std::min(tiles_pb, env_pli));
     while (tiles_pb % pli) --pli;
     return pli;
 }
@@ -1155,21 +1139,11 @@ template <int HW, int PPT, int RP2> static const void *l3_fn3(const bool bwd) {
     return bwd ? (const void *)ss2d_l3_bwd_kernel<HW, PPT, 3, RP2> : (const void *)ss2d_l3_fwd_kernel<HW, PPT, 3, RP2>;
 }
 
-int ss2d_l3_nseg(int batch, int D, int H, int W, int N, int in_dtype);
-// ss2d_w.hpp serves this shape (activated step sizes, fp32 B / C rows): byte offsets inside every tensor fit its 32-bit
-// buffer addressing
-int ss2d_w_covers(int batch, int D, int H, int W, int N, int in_dtype) {
-    if (!w_enabled() || !ss2d_l3_nseg(batch, D, H, W, N, in_dtype)) return 0;
-    const long long planes = (long long)batch * 4 * D, L = (long long)H * W;
-    const long long chk = planes * ((L + 511) / 512) * 256;
-    return (planes * L * 2 < (1ll << 31) && chk < (1ll << 31)) ? 1 : 0;
-}
-
-template <int HW, int PPT> static int l3_launch(const xfm_ss2d_params_t &p, bool bwd, hipStream_t s, float *ws, size_t ws_bytes) {
+template <int HW, int PPT>
+static int l3_launch(const xfm_ss2d_params_t &p, const bool w, bool bwd, hipStream_t s, float *ws, size_t ws_bytes) {
     using G = L3Geom<HW>;
     constexpr int L = G::L, PL = PPT * L;
     const int D = p.d_inner;
-    if (D % PPT) return XFM_ELIMIT;
     LeanArgs la{};
     la.x = p.x; la.dts = p.dts; la.Bs = p.Bs; la.Cs = p.Cs; la.Bs32 = p.Bs32; la.Cs32 = p.Cs32;
     la.A = p.A; la.D = p.D; la.bias = p.delta_bias;
@@ -1180,9 +1154,6 @@ template <int HW, int PPT> static int l3_launch(const xfm_ss2d_params_t &p, bool
     la.magicW = (uint32_t)((0x100000000ull + HW - 1) / HW);
     la.magicL = (uint32_t)((0x100000000ull + L - 1) / L);
     la.magicH = la.magicW;
-    la.dbg = 0;                                        // timing-only switches: 1 skip sweeps, 2 skip plane staging, 4 skip merge,
-    static const int env_dbg = [] { const char *e = getenv("XFM_L3_DBG"); return e ? atoi(e) : 0; }();
-    la.dbg = env_dbg;                                  // 16 no operand prefetch, 32 no ddts / dx stores
     const int tiles_pb = D / PPT;
     const int rp2 = p.delta_softplus == 3 ? l3_rp2(HW, p.dt_rank_p) : 0;
     const int pli = l3_pli(p.batch, tiles_pb, bwd, rp2 > 4 ? 3 : L3_WPE_FWD);
@@ -1205,8 +1176,8 @@ template <int HW, int PPT> static int l3_launch(const xfm_ss2d_params_t &p, bool
         } else {
             return XFM_ELIMIT;
         }
-    } else if (p.delta_softplus == 2 && p.bc_f32) {
-        if (!ss2d_w_covers(p.batch, D, HW, HW, 1, p.in_dtype) || !p.Bs32 || !p.Cs32) return XFM_EINVAL;
+    } else if (w) {
+        if (!p.Bs32 || !p.Cs32) return XFM_EINVAL;
         fn = bwd ? (const void *)ss2d_w_bwd_kernel<HW, PPT> : (const void *)ss2d_w_fwd_kernel<HW, PPT>;
     } else if (bwd)
         fn = p.delta_softplus == 2 ? (const void *)ss2d_l3_bwd_kernel<HW, PPT, 2>
@@ -1216,8 +1187,6 @@ template <int HW, int PPT> static int l3_launch(const xfm_ss2d_params_t &p, bool
         fn = p.delta_softplus == 2 ? (const void *)ss2d_l3_fwd_kernel<HW, PPT, 2>
                                    : (p.delta_softplus == 1 ? (const void *)ss2d_l3_fwd_kernel<HW, PPT, 1>
                                                             : (const void *)ss2d_l3_fwd_kernel<HW, PPT, 0>);
-    static const int env_pad = [] { const char *e = getenv("XFM_L3_LDS_PAD"); return e ? atoi(e) : 0; }();   // occupancy experiments
-    lds += (size_t)env_pad;
     if (lds > 64 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     const unsigned grid = (unsigned)((int64_t)p.batch * (tiles_pb / pli));
     void *kargs[] = {&la};
@@ -1234,57 +1203,60 @@ template <int HW, int PPT> static int l3_launch(const xfm_ss2d_params_t &p, bool
     return check_launch();
 }
 
-// XFM_ELIMIT: shape / dtype not covered here, the caller falls back to the lean / generic kernels
 // planes per tile of the map sizes built here (0: not covered)
 static int l3_ppt(const int H) { return (H == 56 || H == 48) ? 1 : ((H == 28 || H == 24) ? 4 : 0); }
 
-int ss2d_l3_run(const xfm_ss2d_params_t *p, bool bwd, hipStream_t s, float *ws, size_t ws_bytes) {
-    static const bool enabled = [] {
-        const char *e = getenv("XFM_SS2D_L3");
-        return !(e && e[0] == '0');
-    }();
-    if (!enabled) return XFM_ELIMIT;
-    static const bool fwd_enabled = [] {
-        const char *e = getenv("XFM_SS2D_L3_FWD");
-        return !(e && e[0] == '0');
-    }();
-    if (!bwd && !fwd_enabled) return XFM_ELIMIT;
-    if (p->in_dtype != XFM_BF16 || p->out_dtype != XFM_F32 || p->dstate != 1 || p->H != p->W) return XFM_ELIMIT;
-    if (p->bc_f32 && p->delta_softplus != 2) return XFM_EINVAL;
-    if (p->delta_softplus < 0 || p->delta_softplus > 3) return XFM_ELIMIT;
-    if (p->delta_softplus == 3 && !l3_rp2(p->H, p->dt_rank_p)) return XFM_ELIMIT;
-    const int ppt = l3_ppt(p->H);
-    if (!ppt || p->d_inner % ppt) return XFM_ELIMIT;
-    if (!p->chk) return XFM_ELIMIT;            // no checkpoint buffer: the generic path decides (EINVAL if it needs one too)
-    switch (p->H) {
-        case 56: return l3_launch<56, 1>(*p, bwd, s, ws, ws_bytes);
-        case 28: return l3_launch<28, 4>(*p, bwd, s, ws, ws_bytes);
-        case 48: return l3_launch<48, 1>(*p, bwd, s, ws, ws_bytes);   // XFMamba-B at 384 x 384: stages 1 and 2
-        case 24: return l3_launch<24, 4>(*p, bwd, s, ws, ws_bytes);
+// A call the route gave to SS2D_W or SS2D_L3
+int ss2d_l3_run(const xfm_ss2d_params_t &p, SS2DFamily family, bool bwd, hipStream_t s, float *ws, size_t ws_bytes) {
+    const bool w = family == SS2D_W;
+    switch (p.H) {
+        case 56: return l3_launch<56, 1>(p, w, bwd, s, ws, ws_bytes);
+        case 28: return l3_launch<28, 4>(p, w, bwd, s, ws, ws_bytes);
+        case 48: return l3_launch<48, 1>(p, w, bwd, s, ws, ws_bytes);   // XFMamba-B at 384 x 384: stages 1 and 2
+        case 24: return l3_launch<24, 4>(p, w, bwd, s, ws, ws_bytes);
     }
     return XFM_ELIMIT;
 }
 
-// checkpoints per (route, channel) row the kernels of this file write / read: chk[(route * D + d) * NSEG + i], NSEG from THEIR
-// geometry.  0: shape not dispatched here.  xfm_ss2d_plan reports at least this many chunks, so a caller that sizes chk
-// from the plan can never be short whichever kernel family the plan search itself would pick.
-int ss2d_l3_nseg(int batch, int D, int H, int W, int N, int in_dtype) {
-    (void)batch;
-    const char *e = getenv("XFM_SS2D_L3");
-    if ((e && e[0] == '0') || in_dtype != XFM_BF16 || N != 1 || H != W) return 0;
-    const int ppt = l3_ppt(H);
-    if (!ppt || D % ppt) return 0;
-    // ss2d_w.hpp keeps the state entering every LANE's chunk (64 per chunk row); the kernels of this file index the same
-    // buffer with one entry per chunk row
-    return (H * W + 511) / 512 * (w_enabled() ? 64 : 1);
+// A/B switches of the kernel families, read once per process: XFM_SS2D_W=0 sends the calls of ss2d_w.hpp to the kernels of
+// this file, XFM_SS2D_L3=0 sends both to the generic kernels
+static bool family_on(const char *var) {
+    const char *e = getenv(var);
+    return !(e && e[0] == '0');
 }
 
-// padded dt_rank for dt_proj inside the kernels of this file (0: no such kernel)
-int ss2d_l3_dtfused_rank(int batch, int D, int H, int W, int N, int R, int in_dtype) {
-    static const bool off = [] { const char *e = getenv("XFM_L3_DTFUSED"); return e && e[0] == '0'; }();   // A/B switch, read once
-    if (off || !ss2d_l3_nseg(batch, D, H, W, N, in_dtype) || R <= 0) return 0;
-    const int rp = (R + 1) & ~1;
-    return l3_rp2(H, rp) ? rp : 0;
+int ss2d_route(const xfm_ss2d_params_t &p, SS2DRoute &r) {
+    static const bool w_on = family_on("XFM_SS2D_W"), l3_on = family_on("XFM_SS2D_L3");
+    r = SS2DRoute{};
+    if (p.in_dtype < 0 || p.in_dtype > 2 || p.out_dtype != XFM_F32) return XFM_EDTYPE;   // the core always emits fp32 ("oflex")
+    // the wide maps this file and ss2d_w.hpp are built for: bf16 I/O, d_state 1, square, whole tiles of planes
+    const int ppt = l3_ppt(p.H);
+    const bool wide = l3_on && p.in_dtype == XFM_BF16 && p.dstate == 1 && p.H == p.W && ppt && p.d_inner % ppt == 0 &&
+                      p.delta_softplus >= 0 && p.delta_softplus <= 3;
+    const int nseg = (p.H * p.W + 511) / 512;                              // chunk rows of 512 positions
+    if (p.bc_f32) {
+        // fp32 B / C rows beside the activated step sizes: ss2d_w.hpp only, and only where every byte offset inside a tensor
+        // fits its 32-bit buffer addressing
+        const long long planes = (long long)p.batch * 4 * p.d_inner, L = (long long)p.H * p.W;
+        if (!w_on || !wide || p.delta_softplus != 2 || planes * L * 2 >= (1ll << 31) || planes * nseg * 256 >= (1ll << 31))
+            return XFM_EINVAL;
+        r.family = SS2D_W;
+        r.chk_len = 64 * nseg;                         // the state entering every LANE's chunk (64 per chunk row)
+    } else if (wide && (p.delta_softplus != 3 || l3_rp2(p.H, p.dt_rank_p))) {
+        r.family = SS2D_L3;
+        r.chk_len = nseg;                              // one state per chunk row
+    } else {
+        if (p.delta_softplus == 3) return XFM_ELIMIT;  // dt_proj inside the kernel: the kernels of this file only
+        r.family = SS2D_GENERIC;
+        const int rc = plan_ss2d(p.batch, p.d_inner, p.H, p.W, p.dstate, p.in_dtype, &r.plan);
+        r.chk_len = r.plan.n_chunks;
+        return rc;
+    }
+    // the backward's partial-row workspace; XFM_L3_ATOMICS (an A/B switch of the tests, read per call): none, flush by atomics
+    const int tiles_pb = p.d_inner / ppt;
+    const int groups = tiles_pb / l3_pli(p.batch, tiles_pb, true);
+    if (groups > 1 && !getenv("XFM_L3_ATOMICS")) r.ws_bytes = (size_t)p.batch * groups * 4 * 2 * p.H * p.W * sizeof(float);
+    return XFM_OK;
 }
 
 // xr (B4, R, L) -> xrt (B4, nrow, Rp, 64, 8), nrow = ceil(L / 512): the blocked rows the mode-3 kernels read (l3_ops_load).
@@ -1315,16 +1287,6 @@ template <int RP> __global__ void __launch_bounds__(64) l3_xr_rows_kernel(const 
         for (int i = 0; i < 4; ++i) w[i] = (uint32_t)v[8 * j + 2 * i] | ((uint32_t)v[8 * j + 2 * i + 1] << 16);
         *reinterpret_cast<uint4 *>(dst + j * 512) = make_uint4(w[0], w[1], w[2], w[3]);
     }
-}
-
-// bytes of the partial-sum workspace the backward can use (0: shape not covered here)
-size_t ss2d_l3_ws_bytes(const xfm_ss2d_params_t *p) {
-    if (p->in_dtype != XFM_BF16 || p->dstate != 1 || p->H != p->W) return 0;
-    const int ppt = l3_ppt(p->H);
-    if (!ppt || p->d_inner % ppt) return 0;
-    const int tiles_pb = p->d_inner / ppt;
-    const int groups = tiles_pb / l3_pli(p->batch, tiles_pb, true);
-    return groups > 1 ? (size_t)p->batch * groups * 4 * 2 * p->H * p->W * sizeof(float) : 0;
 }
 
 }  // namespace xfm

@@ -29,7 +29,6 @@ struct LeanArgs {
     int ppt;         // planes per tile (staged together in LDS)
     int pli;         // tiles per workgroup
     int softplus;
-    int dbg;         // timing-only switches (XFM_SS2D_DBG): 1 skip sweeps, 2 skip plane loads, 4 skip merge/store, 8 skip dB/dC flush
     uint32_t magicW;
     uint32_t magicL;   // ceil(2^32 / L): plane index of a tile element by multiply-high (tile elements < 2^16)
     uint32_t magicH;   // ceil(2^32 / H)
@@ -739,21 +738,19 @@ __global__ void __launch_bounds__(256) ss2d_fwd_lean_kernel(const LeanArgs a) {
     constexpr int NVX = BIG ? 5 : (C == 8 ? 2 : 4);    // ppt*L <= 3200 elements (plan), BIG: one plane <= 10240
     constexpr bool kPipe = sizeof(Tin) == 2 && C == 8;  // as in the backward: next tile's planes in flight during the sweeps
     PlaneRegs<Tin, C, NVX> px;
-    if (kPipe && !(a.dbg & 2))
+    if (kPipe)
         lean_planes_issue<Tin, C, NVX>(a, px, (const Tin *)a.x + ((int64_t)b * D + (int64_t)tg * a.pli * a.ppt) * L, PL);
     for (int it = 0; it < a.pli; ++it) {
         const int d0 = (tg * a.pli + it) * a.ppt;
         const int64_t po = ((int64_t)b * D + d0) * L;
         __syncthreads();
-        if (!(a.dbg & 2)) {
-            // (not pipelined: still ONE round trip for the whole tile -- the per-plane loop of lean_planes_load is a
-            //  chain of ppt dependent HBM latencies)
-            if (!kPipe) lean_planes_issue<Tin, C, NVX>(a, px, (const Tin *)a.x + po, PL);
-            lean_planes_commit<Tin, Tin, C, NVX>(a, px, xN, xT, PL);
-        }
+        // (not pipelined: still ONE round trip for the whole tile -- the per-plane loop of lean_planes_load is a
+        //  chain of ppt dependent HBM latencies)
+        if (!kPipe) lean_planes_issue<Tin, C, NVX>(a, px, (const Tin *)a.x + po, PL);
+        lean_planes_commit<Tin, Tin, C, NVX>(a, px, xN, xT, PL);
         __syncthreads();
-        if (kPipe && !(a.dbg & 2) && it + 1 < a.pli) lean_planes_issue<Tin, C, NVX>(a, px, (const Tin *)a.x + po + PL, PL);
-        for (int pl = 0; pl < ((a.dbg & 1) ? 0 : a.ppt); ++pl) {
+        if (kPipe && it + 1 < a.pli) lean_planes_issue<Tin, C, NVX>(a, px, (const Tin *)a.x + po + PL, PL);
+        for (int pl = 0; pl < a.ppt; ++pl) {
             const int d = d0 + pl, row = k * D + d;
             const Tin *dts_row = (const Tin *)a.dts + (route * D + d) * L;
             float *chk_row = a.chk + (route * D + d) * a.nseg;
@@ -763,7 +760,6 @@ __global__ void __launch_bounds__(256) ss2d_fwd_lean_kernel(const LeanArgs a) {
             else lean_fwd_plane<Tin, C, false>(a, dts_row, Brow, Crow, chk_row, A2, Dr, bias, xq + pl * L, yq + pl * L, lane, pf, has_next);
         }
         __syncthreads();
-        if (a.dbg & 4) continue;
         lean_merge_store<Tin, Tout, C>(a, (Tout *)a.y + po, Y, Y + PL, Y + 2 * PL, Y + 3 * PL, PL);   // fixed order
     }
 }
@@ -838,7 +834,7 @@ ss2d_bwd_lean_kernel(const LeanArgs a) {
     constexpr bool kPipe = sizeof(Tin) == 2 && sizeof(Tout) == 4 && C == 8 && !BIG;   // (BIG: the registers hold the sums)
     PlaneRegs<Tin, C, NVX> px;
     PlaneRegs<Tout, 4, NVG> pg;
-    if (kPipe && !(a.dbg & 2)) {
+    if (kPipe) {
         const int64_t po0 = ((int64_t)b * D + (int64_t)tg * a.pli * a.ppt) * L;
         lean_planes_issue<Tin, C, NVX>(a, px, (const Tin *)a.x + po0, PL);
         lean_planes_issue<Tout, 4, NVG>(a, pg, (const Tout *)a.dy + po0, PL);
@@ -847,20 +843,18 @@ ss2d_bwd_lean_kernel(const LeanArgs a) {
         const int d0 = (tg * a.pli + it) * a.ppt;
         const int64_t po = ((int64_t)b * D + d0) * L;
         __syncthreads();
-        if (!(a.dbg & 2)) {
-            if (!kPipe) {                               // one round trip for the tile (see the forward kernel)
-                lean_planes_issue<Tin, C, NVX>(a, px, (const Tin *)a.x + po, PL);
-                lean_planes_issue<Tout, 4, NVG>(a, pg, (const Tout *)a.dy + po, PL);
-            }
-            lean_planes_commit<Tin, Tin, C, NVX>(a, px, xN, xT, PL);
-            lean_planes_commit<Tout, Tin, 4, NVG>(a, pg, gN, gT, PL);
+        if (!kPipe) {                                   // one round trip for the tile (see the forward kernel)
+            lean_planes_issue<Tin, C, NVX>(a, px, (const Tin *)a.x + po, PL);
+            lean_planes_issue<Tout, 4, NVG>(a, pg, (const Tout *)a.dy + po, PL);
         }
+        lean_planes_commit<Tin, Tin, C, NVX>(a, px, xN, xT, PL);
+        lean_planes_commit<Tout, Tin, 4, NVG>(a, pg, gN, gT, PL);
         __syncthreads();
-        if (kPipe && !(a.dbg & 2) && it + 1 < a.pli) {
+        if (kPipe && it + 1 < a.pli) {
             lean_planes_issue<Tin, C, NVX>(a, px, (const Tin *)a.x + po + PL, PL);
             lean_planes_issue<Tout, 4, NVG>(a, pg, (const Tout *)a.dy + po + PL, PL);
         }
-        for (int pl = 0; pl < ((a.dbg & 1) ? 0 : a.ppt); ++pl) {
+        for (int pl = 0; pl < a.ppt; ++pl) {
             const int d = d0 + pl, row = k * D + d;
             const int64_t ro = (route * D + d) * L;
             const float *chk_row = a.chk + (route * D + d) * nseg;
@@ -886,11 +880,9 @@ ss2d_bwd_lean_kernel(const LeanArgs a) {
             }
         }
         __syncthreads();
-        if (a.dbg & 4) continue;
         lean_merge_store<Tin, Tin, C>(a, (Tin *)a.dx + po, DX, DX + PL, DX + 2 * PL, DX + 3 * PL, PL);
     }
     wave_sync();
-    if (a.dbg & 8) return;
     float *dBg = a.dBs + route * L, *dCg = a.dCs + route * L;
     if constexpr (NSEG > 0) {
         // registers hold [traversal chunk s][traversal element j] of this lane.  Atomics are only fast when a

@@ -21,6 +21,10 @@
 
 namespace xfm {
 
+// the backward stages the next tile by LDS-direct loads into the second x image and the raw dy region, which l3_launch
+// sizes only in a prefetching build
+static_assert(L3_PREFETCH, "ss2d_w.hpp: the backward's LDS layout needs L3_PREFETCH (ss2d_l3.hip)");
+
 struct WOps { uint4 d, b0, b1, c0, c1; float h; };      // step sizes (8 bf16), B and C (8 fp32 each), the entering state
 
 // Global operands through BUFFER descriptors: address = descriptor base (4 scalar registers per tensor) + scalar byte offset

@@ -58,10 +58,14 @@ def to_route_order(t: torch.Tensor, H: int, W: int) -> torch.Tensor:
     return torch.stack([t[:, :, 0].flatten(-2), t[:, :, 1].transpose(-1, -2).flatten(-2)], dim=2).view(B, K, C, L)
 
 
-def _plan(Bt, Dm, H, W, N, dtype):
-    plan = _lib.ScanPlan()
-    _lib.check(_lib.lib().xfm_ss2d_plan(Bt, Dm, H, W, N, _lib.dtype_code(dtype), ctypes.byref(plan)), "ss2d_plan")
-    return plan
+def _alloc_chk(p, device):
+    """The chunk-state buffer of the call ``p`` describes (filled but for ``chk``), sized for the kernel family that serves
+    it; set as ``p.chk``.  None when the call needs none."""
+    n = _lib.lib().xfm_ss2d_chk_chunks(ctypes.byref(p))
+    _lib.check(min(n, 0), "ss2d_chk_chunks")
+    chk = torch.empty((p.batch, 4, p.d_inner, n, p.dstate), dtype=torch.float32, device=device) if n > 1 else None
+    p.chk = _lib.ptr(chk)
+    return chk
 
 
 def _fill(p, x, dts, A, Bs, Cs, D, bias, H, W, out_dtype, chk, softplus_mode=1, xrt=None, dt_w=None, bc32=None):
@@ -91,12 +95,10 @@ class SS2DCoreHip(torch.autograd.Function):
             raise RuntimeError("ss2d_core: x, dts, Bs, Cs must share one dtype")
         x, dts, Bs, Cs = x.contiguous(), dts.contiguous(), Bs.contiguous(), Cs.contiguous()
         A, D, bias = A.float().contiguous(), D.float().contiguous(), bias.float().contiguous()
-        plan = _plan(Bt, Dm, H, W, N, x.dtype)
-        chk = (torch.empty((Bt, 4, Dm, plan.n_chunks, N), dtype=torch.float32, device=x.device)
-               if plan.n_chunks > 1 else None)
         y = torch.empty((Bt, Dm, L), dtype=torch.float32, device=x.device)   # oflex: fp32 out
         p = _lib.SS2DParams()
-        _fill(p, x, dts, A, Bs, Cs, D, bias, H, W, torch.float32, chk)
+        _fill(p, x, dts, A, Bs, Cs, D, bias, H, W, torch.float32, None)
+        chk = _alloc_chk(p, x.device)
         p.y = y.data_ptr()
         isz = x.element_size()
         nbytes = Bt * Dm * L * (5 * isz + 4) + 2 * Bt * 4 * N * L * isz            # SURVEY 8(d), fused boundary
@@ -228,12 +230,10 @@ class SS2DProjCoreHip(torch.autograd.Function):
         else:
             _note_library_fallback("dt_proj forward", Bt, Dm, R, L)
             dts = torch.matmul(w, xr)
-        plan = _plan(Bt, Dm, H, W, N, x.dtype)
-        chk = (torch.empty((Bt, 4, Dm, plan.n_chunks, N), dtype=torch.float32, device=x.device)
-               if plan.n_chunks > 1 else None)
         y = torch.empty((Bt, Dm, L), dtype=torch.float32, device=x.device)
         p = _lib.SS2DParams()
-        _fill(p, x, dts, A, Bs, Cs, D, bias, H, W, torch.float32, chk, mode, xrt, wp, b32)
+        _fill(p, x, dts, A, Bs, Cs, D, bias, H, W, torch.float32, None, mode, xrt, wp, b32)
+        chk = _alloc_chk(p, x.device)
         p.y = y.data_ptr()
         isz = x.element_size()
         # SURVEY 8(d), "dt_proj also fused" boundary: x, y and the x_proj rows (2 B D L + 4 B (R + 2N) L elements)
