@@ -19,6 +19,10 @@
  *   xfm_cross_scan          <- CrossScanTritonF.forward / triton_cross_scan_flex,
  *                              models/csm_triton.py:403-430, 278-400 (scans=0, channel-first)
  *   xfm_cross_merge         <- CrossMergeTritonF.forward, models/csm_triton.py:456-483
+ *   xfm_cross_scan_flex     <- CrossScanTritonF.forward / triton_cross_scan_flex, models/csm_triton.py:403-430,
+ *                              279-400 (every x / y layout, one_by_one, scans 0 / 1 / 2; dispatch at :501-507)
+ *   xfm_cross_merge_flex    <- CrossMergeTritonF.forward / CrossScanTritonF.backward, models/csm_triton.py:456-483,
+ *                              432-453 (the same configurations; dispatch at :511-517)
  *   xfm_swap_scan           <- SwappingScan_multiview.forward, models/fusion_vmamba.py:189-213
  *   xfm_dwconv3x3_fwd/_bwd  <- `self.conv2d` (nn.Conv2d(D, D, 3, padding=1, groups=D)) followed by `self.act`
  *                              (nn.SiLU) in front of every SS2D core: models/fusion_vmamba.py:1198-1201,
@@ -109,6 +113,17 @@ int xfm_cross_scan(const void *x, void *y, int B, int C, int H, int W, int dtype
 /* y: (B, 4, C, H*W) contiguous (in_dtype) -> x: (B, C, H*W) contiguous (out_dtype);
  * x = y0 + flip(y2) + T^-1(y1 + flip(y3)), accumulated in fp32. */
 int xfm_cross_merge(const void *y, void *x, int B, int C, int H, int W, int in_dtype, int out_dtype, void *stream);
+/* Every route configuration of triton_cross_scan_flex.  x_layout / y_layout: 0 channel-first, 1 channel-last;
+ * x: (B, C, H*W) | (B, H*W, C), or with one_by_one = 1 (B, 4, C, H*W) | (B, H*W, 4, C);  y: (B, 4, C, H*W) | (B, H*W, 4, C).
+ * scans: 0 cross2d (the routes of xfm_cross_scan), 1 unidirectional (all four routes row-major),
+ * 2 bidirectional (routes 0, 1 row-major, routes 2, 3 their flip).  Scan: y_k[q_k(p)] = x[p] (one_by_one: x_k[p]).
+ * Merge: x[p] = sum_k y_k[q_k(p)] accumulated in fp32 (one_by_one: x_k[p] = y_k[q_k(p)]), written as out_dtype.
+ * All tensors contiguous.  A flag outside its range, scans outside {0, 1, 2} or B > 65535 is XFM_EINVAL.  The
+ * channel-first, scans = 0, one_by_one = 0 configuration runs xfm_cross_scan / xfm_cross_merge. */
+int xfm_cross_scan_flex(const void *x, void *y, int B, int C, int H, int W, int x_layout, int y_layout, int one_by_one,
+                        int scans, int dtype, void *stream);
+int xfm_cross_merge_flex(const void *y, void *x, int B, int C, int H, int W, int x_layout, int y_layout, int one_by_one,
+                         int scans, int in_dtype, int out_dtype, void *stream);
 /* x, x2: (B, C, L) contiguous -> out: (B, 2, C, L): out[:,0] = x with even channels from x2,
  * out[:,1] = x2 with even channels from x. */
 int xfm_swap_scan(const void *x, const void *x2, void *out, int B, int C, int L, int dtype, void *stream);

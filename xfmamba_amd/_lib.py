@@ -20,7 +20,7 @@ _DT = {torch.float32: XFM_F32, torch.float16: XFM_F16, torch.bfloat16: XFM_BF16}
 # every symbol include/xfm_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = (
     "xfm_abi_version", "xfm_strerror", "xfm_last_hip_error", "xfm_prof_main_kernel", "xfm_scan_plan",
-    "xfm_selective_scan_fwd", "xfm_selective_scan_bwd", "xfm_cross_scan", "xfm_cross_merge",
+    "xfm_selective_scan_fwd", "xfm_selective_scan_bwd", "xfm_cross_scan", "xfm_cross_merge", "xfm_cross_scan_flex", "xfm_cross_merge_flex",
     "xfm_swap_scan", "xfm_ss2d_route_split", "xfm_ss2d_route_merge", "xfm_ss2d_dt_proj_supported", "xfm_ss2d_dt_proj_mfma_rp", "xfm_ss2d_dt_proj_fwd_mfma", "xfm_ss2d_dt_proj_bwd_mfma", "xfm_ss2d_dt_proj_fwd",
     "xfm_dwconv3x3_fwd", "xfm_dwconv3x3_bwd", "xfm_dwconv3x3_tokens_supported", "xfm_dwconv3x3_tokens_fwd", "xfm_dwconv3x3_tokens_bwd", "xfm_conv3x3s2_tokens_supported", "xfm_conv3x3s2_tokens_fwd", "xfm_conv3x3s2_tokens_bwd_data", "xfm_conv3x3s2_tokens_bwd_weight", "xfm_conv3x3s2_tokens_bwd_weight_x_supported", "xfm_conv3x3s2_tokens_bwd_weight_x", "xfm_conv3x3s2_gray_supported", "xfm_conv3x3s2_gray_ws_floats", "xfm_conv3x3s2_gray_fwd", "xfm_conv3x3s2_gray_bwd_weight", "xfm_layernorm2d_fwd", "xfm_layernorm2d_bwd", "xfm_layernorm2d_bwd_parts_blocks", "xfm_layernorm2d_bwd_parts", "xfm_layernorm2d_ws_floats", "xfm_layernorm2d_bwd_ws_floats", "xfm_layernorm2d_bwd_ws_blocks", "xfm_layernorm2d_fwd_ws", "xfm_layernorm2d_bwd_parts_ws",
     "xfm_add_layernorm_rows_supported", "xfm_add_layernorm_rows_bwd_blocks", "xfm_add_layernorm_rows_fwd",
@@ -147,6 +147,8 @@ def lib() -> C.CDLL:
         l.xfm_wgrad.argtypes = [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_int64] * 2 + [C.c_int] * 2 + [C.c_void_p]
         l.xfm_cross_scan.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]
         l.xfm_cross_merge.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]
+        l.xfm_cross_scan_flex.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 9 + [C.c_void_p]
+        l.xfm_cross_merge_flex.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 10 + [C.c_void_p]
         l.xfm_swap_scan.argtypes = [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p]
         l.xfm_dwconv3x3_fwd.argtypes = [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p]
         l.xfm_dwconv3x3_bwd.argtypes = [C.c_void_p] * 7 + [C.c_int] * 6 + [C.c_void_p]

@@ -223,6 +223,267 @@ static int launch_route(bool merge, const void *a, const void *b, const void *c,
     return check_launch();
 }
 
+// ---- flexible routes (xfm_cross_scan_flex / xfm_cross_merge_flex) ----------------------------------------------
+// Index maps of triton_cross_scan_flex (models/csm_triton.py:279-400): route k's position q for the map position
+// p = h*W + w is
+//   scans 0 (cross2d): q0 = p, q1 = w*H + h, q2 = L-1-q0, q3 = L-1-q1
+//   scans 1 (unidi):   q0 = q1 = q2 = q3 = p
+//   scans 2 (bidi):    q0 = q1 = p, q2 = q3 = L-1-p
+// scan: y_k[q_k(p)] = x[p] (one_by_one: x_k[p]);  merge: x[p] = sum_k y_k[q_k(p)] in fp32 (one_by_one: x_k[p] = y_k[q_k(p)]).
+// x is (B, C, L) channel-first or (B, L, C) channel-last, with a route axis (B, 4, C, L) / (B, L, 4, C) under one_by_one;
+// y is (B, 4, C, L) or (B, L, 4, C).  Three kernels serve the configurations:
+//   flex_rows_kernel   both sides channel-last: every route moves whole C-rows, vector loads / stores along C;
+//   flex_planes_kernel both sides channel-first, no transposed route (scans 1/2): vector loads / stores along L, the
+//                      flipped routes reverse the vector in registers;
+//   flex_tile_kernel   everything else (layouts differ, or one_by_one cross2d channel-first): a (channels x rows x
+//                      columns) tile staged in LDS, read and written with lanes along each side's contiguous axis.
+// Scans move raw bits (Ti == To == uint16_t / float); merges convert through fp32 (Ti, To = float / f16_t / bf16_t).
+
+template <typename T> struct Elt;
+template <> struct Elt<float> {
+    static __device__ __forceinline__ float get(float v) { return v; }
+    static __device__ __forceinline__ float put(float v) { return v; }
+};
+template <> struct Elt<uint16_t> {  // 16-bit payload carried bit-exact through a 32-bit register / LDS word
+    static __device__ __forceinline__ float get(uint16_t v) { return __uint_as_float(v); }
+    static __device__ __forceinline__ uint16_t put(float v) { return (uint16_t)__float_as_uint(v); }
+};
+template <> struct Elt<bf16_t> {
+    static __device__ __forceinline__ float get(bf16_t v) { return ldf<bf16_t>(&v); }
+    static __device__ __forceinline__ bf16_t put(float v) { return __float2bfloat16(v); }
+};
+template <> struct Elt<f16_t> {
+    static __device__ __forceinline__ float get(f16_t v) { return __half2float(v); }
+    static __device__ __forceinline__ f16_t put(float v) { return __float2half(v); }
+};
+
+template <typename T, int V> struct alignas(sizeof(T) * V) Vec { T v[V]; };
+
+__device__ __forceinline__ bool route_flipped(int k, int scans) { return scans != 1 && k >= 2; }
+__device__ __forceinline__ bool route_transposed(int k, int scans) { return scans == 0 && (k & 1); }
+__device__ __forceinline__ int64_t route_pos(int k, int scans, int h, int w, int H, int W) {
+    const int64_t L = (int64_t)H * W;
+    const int64_t q = route_transposed(k, scans) ? (int64_t)w * H + h : (int64_t)h * W + w;
+    return route_flipped(k, scans) ? L - 1 - q : q;
+}
+
+// both sides channel-last; one item = V channels of one map position.  src / dst: x / y for the scan, y / x for the merge.
+template <bool MERGE, typename Ti, typename To, int V>
+__global__ void __launch_bounds__(256) flex_rows_kernel(const Ti *__restrict__ src, To *__restrict__ dst, int B, int C,
+                                                        int H, int W, int obo, int scans) {
+    const int64_t L = (int64_t)H * W, nv = C / V, total = (int64_t)B * L * nv;
+    for (int64_t it = (int64_t)blockIdx.x * 256 + threadIdx.x; it < total; it += (int64_t)gridDim.x * 256) {
+        const int64_t row = it / nv;
+        const int ch = (int)(it - row * nv) * V;
+        const int64_t b = row / L, p = row - b * L;
+        const int h = (int)(p / W), w = (int)(p - (int64_t)h * W);
+        const int64_t xrow = obo ? row * 4 * C + ch : row * C + ch;  // + k*C under one_by_one
+        if (!MERGE) {
+            Vec<Ti, V> v = *(const Vec<Ti, V> *)(src + xrow);
+            for (int k = 0; k < 4; ++k) {
+                if (obo && k) v = *(const Vec<Ti, V> *)(src + xrow + (int64_t)k * C);
+                Vec<To, V> o;
+#pragma unroll
+                for (int i = 0; i < V; ++i) o.v[i] = Elt<To>::put(Elt<Ti>::get(v.v[i]));
+                *(Vec<To, V> *)(dst + ((b * L + route_pos(k, scans, h, w, H, W)) * 4 + k) * C + ch) = o;
+            }
+        } else {
+            float acc[V];
+            for (int k = 0; k < 4; ++k) {
+                const Vec<Ti, V> v = *(const Vec<Ti, V> *)(src + ((b * L + route_pos(k, scans, h, w, H, W)) * 4 + k) * C + ch);
+#pragma unroll
+                for (int i = 0; i < V; ++i) acc[i] = (obo || k == 0) ? Elt<Ti>::get(v.v[i]) : acc[i] + Elt<Ti>::get(v.v[i]);
+                if (obo || k == 3) {
+                    Vec<To, V> o;
+#pragma unroll
+                    for (int i = 0; i < V; ++i) o.v[i] = Elt<To>::put(acc[i]);
+                    *(Vec<To, V> *)(dst + xrow + (obo ? (int64_t)k * C : 0)) = o;
+                }
+            }
+        }
+    }
+}
+
+// both sides channel-first, scans 1 or 2 (routes are the identity or a flip of L); one item = V positions of one plane.
+template <bool MERGE, typename Ti, typename To, int V>
+__global__ void __launch_bounds__(256) flex_planes_kernel(const Ti *__restrict__ src, To *__restrict__ dst, int B, int C,
+                                                          int64_t L, int obo, int scans) {
+    const int64_t nv = L / V, total = (int64_t)B * C * nv;
+    for (int64_t it = (int64_t)blockIdx.x * 256 + threadIdx.x; it < total; it += (int64_t)gridDim.x * 256) {
+        const int64_t plane = it / nv, p = (it - plane * nv) * V;
+        const int64_t b = plane / C, c = plane - b * C;
+        const int64_t xp = obo ? (b * 4 * C + c) * L + p : plane * L + p;  // + k*C*L under one_by_one
+        auto yat = [&](int k) { return ((b * 4 + k) * C + c) * L + (route_flipped(k, scans) ? L - p - V : p); };
+        if (!MERGE) {
+            Vec<Ti, V> v = *(const Vec<Ti, V> *)(src + xp);
+            for (int k = 0; k < 4; ++k) {
+                if (obo && k) v = *(const Vec<Ti, V> *)(src + xp + (int64_t)k * C * L);
+                const bool f = route_flipped(k, scans);
+                Vec<To, V> o;
+#pragma unroll
+                for (int i = 0; i < V; ++i) o.v[i] = Elt<To>::put(Elt<Ti>::get(v.v[f ? V - 1 - i : i]));
+                *(Vec<To, V> *)(dst + yat(k)) = o;
+            }
+        } else {
+            float acc[V];
+            for (int k = 0; k < 4; ++k) {
+                const Vec<Ti, V> v = *(const Vec<Ti, V> *)(src + yat(k));
+                const bool f = route_flipped(k, scans);
+#pragma unroll
+                for (int i = 0; i < V; ++i) {
+                    const float e = Elt<Ti>::get(v.v[f ? V - 1 - i : i]);
+                    acc[i] = (obo || k == 0) ? e : acc[i] + e;
+                }
+                if (obo || k == 3) {
+                    Vec<To, V> o;
+#pragma unroll
+                    for (int i = 0; i < V; ++i) o.v[i] = Elt<To>::put(acc[i]);
+                    *(Vec<To, V> *)(dst + xp + (obo ? (int64_t)k * C * L : 0)) = o;
+                }
+            }
+        }
+    }
+}
+
+// Tile walk orders: lanes along the columns (w), along the rows (h) or along the channels.  A channel-first side walks w
+// for row-major positions and h for the column-major (transposed) routes; a channel-last side walks the channels.
+enum { WALK_W = 0, WALK_H = 1, WALK_C = 2 };
+
+template <int TC, int TH, int TW>
+struct Tile {
+    static constexpr int RP = TW + 1;            // odd row pitch: a walk along h is bank-conflict free
+    static constexpr int CP = (TH * RP) | 1;     // odd channel pitch: a walk along the channels is bank-conflict free
+    static constexpr int N = TC * TH * TW;
+    struct Idx { int cc, hh, ww; };
+    static __device__ __forceinline__ Idx at(int walk, int e) {
+        if (walk == WALK_W) return {e / (TW * TH), (e / TW) % TH, e % TW};
+        if (walk == WALK_H) return {e / (TH * TW), e % TH, (e / TH) % TW};
+        return {e % TC, e / (TC * TW), (e / TC) % TW};
+    }
+};
+
+template <bool MERGE, typename Ti, typename To, int TC, int TH, int TW>
+__global__ void __launch_bounds__(256) flex_tile_kernel(const Ti *__restrict__ src, To *__restrict__ dst, int C, int H, int W,
+                                                        int xcl, int ycl, int obo, int scans) {
+    using T = Tile<TC, TH, TW>;
+    __shared__ float S[TC * T::CP];
+    const int ntw = (W + TW - 1) / TW;
+    const int h0 = (blockIdx.x / ntw) * TH, w0 = (blockIdx.x % ntw) * TW, c0 = blockIdx.y * TC;
+    const int64_t b = blockIdx.z, L = (int64_t)H * W;
+    const int xwalk = xcl ? WALK_C : WALK_W;
+    auto ywalk = [&](int k) { return ycl ? WALK_C : (route_transposed(k, scans) ? WALK_H : WALK_W); };
+    // element offsets; the x route axis exists only under one_by_one
+    auto xoff = [&](int k, int c, int h, int w) -> int64_t {
+        const int64_t p = (int64_t)h * W + w;
+        if (!obo) return xcl ? (b * L + p) * C + c : (b * C + c) * L + p;
+        return xcl ? ((b * L + p) * 4 + k) * C + c : ((b * 4 + k) * C + c) * L + p;
+    };
+    auto yoff = [&](int k, int c, int h, int w) -> int64_t {
+        const int64_t q = route_pos(k, scans, h, w, H, W);
+        return ycl ? ((b * L + q) * 4 + k) * C + c : ((b * 4 + k) * C + c) * L + q;
+    };
+    // visit every in-range element of the tile in walk order: f(lds index, c, h, w)
+    auto walk = [&](int order, auto f) {
+        for (int e = threadIdx.x; e < T::N; e += 256) {
+            const auto i = T::at(order, e);
+            const int c = c0 + i.cc, h = h0 + i.hh, w = w0 + i.ww;
+            if (c < C && h < H && w < W) f(i.cc * T::CP + i.hh * T::RP + i.ww, c, h, w);
+        }
+    };
+    if (!MERGE) {
+        for (int k = 0; k < 4; ++k) {
+            if (k == 0 || obo) {
+                if (k) __syncthreads();
+                walk(xwalk, [&](int s, int c, int h, int w) { S[s] = Elt<Ti>::get(src[xoff(k, c, h, w)]); });
+                __syncthreads();
+            }
+            walk(ywalk(k), [&](int s, int c, int h, int w) { dst[yoff(k, c, h, w)] = Elt<To>::put(S[s]); });
+        }
+    } else {
+        for (int k = 0; k < 4; ++k) {
+            const bool first = k == 0 || obo;
+            walk(ywalk(k), [&](int s, int c, int h, int w) {
+                const float v = Elt<Ti>::get(src[yoff(k, c, h, w)]);
+                S[s] = first ? v : S[s] + v;
+            });
+            __syncthreads();
+            if (obo || k == 3) {
+                walk(xwalk, [&](int s, int c, int h, int w) { dst[xoff(k, c, h, w)] = Elt<To>::put(S[s]); });
+                __syncthreads();
+            }
+        }
+    }
+}
+
+static bool aligned(const void *p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+// widest vector (<= 16 bytes on either side) that divides n and that both base pointers are aligned for
+template <typename Ti, typename To>
+static int vec_width(int64_t n, const void *a, const void *b) {
+    for (int v = 8; v > 1; v /= 2)
+        if (v * sizeof(Ti) <= 16 && v * sizeof(To) <= 16 && n % v == 0 && aligned(a, v * sizeof(Ti)) &&
+            aligned(b, v * sizeof(To)))
+            return v;
+    return 1;
+}
+
+static unsigned stride_grid(int64_t items) {
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + 255) / 256, 256 * 32));
+}
+
+template <bool MERGE, typename Ti, typename To, int V>
+static void launch_rows_v(const void *s, void *d, int B, int C, int H, int W, int obo, int scans, hipStream_t st) {
+    hipLaunchKernelGGL((flex_rows_kernel<MERGE, Ti, To, V>), dim3(stride_grid((int64_t)B * H * W * (C / V))), dim3(256),
+                       0, st, (const Ti *)s, (To *)d, B, C, H, W, obo, scans);
+}
+
+template <bool MERGE, typename Ti, typename To, int V>
+static void launch_planes_v(const void *s, void *d, int B, int C, int64_t L, int obo, int scans, hipStream_t st) {
+    hipLaunchKernelGGL((flex_planes_kernel<MERGE, Ti, To, V>), dim3(stride_grid((int64_t)B * C * (L / V))), dim3(256),
+                       0, st, (const Ti *)s, (To *)d, B, C, L, obo, scans);
+}
+
+template <bool MERGE, typename Ti, typename To, int TC, int TH, int TW>
+static void launch_tile(const void *s, void *d, int B, int C, int H, int W, int xcl, int ycl, int obo, int scans,
+                        hipStream_t st) {
+    const dim3 grid((unsigned)(((H + TH - 1) / TH) * ((W + TW - 1) / TW)), (unsigned)((C + TC - 1) / TC), (unsigned)B);
+    hipLaunchKernelGGL((flex_tile_kernel<MERGE, Ti, To, TC, TH, TW>), grid, dim3(256), 0, st, (const Ti *)s, (To *)d, C, H,
+                       W, xcl, ycl, obo, scans);
+}
+
+// s / d: x / y for the scan, y / x for the merge.  The channel-first cross2d configuration without one_by_one is the
+// caller's (xfm_cross_scan / xfm_cross_merge).
+template <bool MERGE, typename Ti, typename To>
+static int launch_flex(const void *s, void *d, int B, int C, int H, int W, int xcl, int ycl, int obo, int scans,
+                       hipStream_t st) {
+    const int64_t L = (int64_t)H * W;
+    if (xcl && ycl) {
+        switch (vec_width<Ti, To>(C, s, d)) {
+            case 8: launch_rows_v<MERGE, Ti, To, 8>(s, d, B, C, H, W, obo, scans, st); break;
+            case 4: launch_rows_v<MERGE, Ti, To, 4>(s, d, B, C, H, W, obo, scans, st); break;
+            case 2: launch_rows_v<MERGE, Ti, To, 2>(s, d, B, C, H, W, obo, scans, st); break;
+            default: launch_rows_v<MERGE, Ti, To, 1>(s, d, B, C, H, W, obo, scans, st);
+        }
+    } else if (!xcl && !ycl && scans != 0) {
+        switch (vec_width<Ti, To>(L, s, d)) {
+            case 8: launch_planes_v<MERGE, Ti, To, 8>(s, d, B, C, L, obo, scans, st); break;
+            case 4: launch_planes_v<MERGE, Ti, To, 4>(s, d, B, C, L, obo, scans, st); break;
+            case 2: launch_planes_v<MERGE, Ti, To, 2>(s, d, B, C, L, obo, scans, st); break;
+            default: launch_planes_v<MERGE, Ti, To, 1>(s, d, B, C, L, obo, scans, st);
+        }
+    } else if (!xcl && !ycl) {
+        launch_tile<MERGE, Ti, To, 1, 64, 64>(s, d, B, C, H, W, xcl, ycl, obo, scans, st);  // plane transposes
+    } else {
+        launch_tile<MERGE, Ti, To, 16, 16, 16>(s, d, B, C, H, W, xcl, ycl, obo, scans, st);
+    }
+    return check_launch();
+}
+
+static bool flex_args_ok(const void *a, const void *b, int B, int C, int H, int W, int xl, int yl, int obo, int scans) {
+    return a && b && B > 0 && C > 0 && H > 0 && W > 0 && (xl == 0 || xl == 1) && (yl == 0 || yl == 1) &&
+           (obo == 0 || obo == 1) && scans >= 0 && scans <= 2 && B <= 65535 && (int64_t)H * W <= INT32_MAX;
+}
+
 }  // namespace xfm
 
 extern "C" {
@@ -311,5 +572,37 @@ int xfm_swap_scan(const void *x, const void *x2, void *out, int B, int C, int L,
         default: return XFM_EDTYPE;
     }
     return check_launch();
+}
+
+int xfm_cross_scan_flex(const void *x, void *y, int B, int C, int H, int W, int x_layout, int y_layout, int one_by_one,
+                        int scans, int dtype, void *stream) {
+    using namespace xfm;
+    if (!flex_args_ok(x, y, B, C, H, W, x_layout, y_layout, one_by_one, scans)) return XFM_EINVAL;
+    if (dtype != XFM_F32 && dtype != XFM_F16 && dtype != XFM_BF16) return XFM_EDTYPE;
+    if (!x_layout && !y_layout && !one_by_one && scans == 0) return xfm_cross_scan(x, y, B, C, H, W, dtype, stream);
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == XFM_F32) return launch_flex<false, float, float>(x, y, B, C, H, W, x_layout, y_layout, one_by_one, scans, s);
+    return launch_flex<false, uint16_t, uint16_t>(x, y, B, C, H, W, x_layout, y_layout, one_by_one, scans, s);
+}
+
+int xfm_cross_merge_flex(const void *y, void *x, int B, int C, int H, int W, int x_layout, int y_layout, int one_by_one,
+                         int scans, int in_dtype, int out_dtype, void *stream) {
+    using namespace xfm;
+    if (!flex_args_ok(y, x, B, C, H, W, x_layout, y_layout, one_by_one, scans)) return XFM_EINVAL;
+    if (!x_layout && !y_layout && !one_by_one && scans == 0)
+        return xfm_cross_merge(y, x, B, C, H, W, in_dtype, out_dtype, stream);
+    hipStream_t s = (hipStream_t)stream;
+    const int a = x_layout, b = y_layout, o = one_by_one;
+#define XFM_MERGE_FLEX(I, O, TI, TO) \
+    if (in_dtype == I && out_dtype == O) return launch_flex<true, TI, TO>(y, x, B, C, H, W, a, b, o, scans, s);
+    XFM_MERGE_FLEX(XFM_F32, XFM_F32, float, float)
+    XFM_MERGE_FLEX(XFM_F32, XFM_BF16, float, bf16_t)
+    XFM_MERGE_FLEX(XFM_F32, XFM_F16, float, f16_t)
+    XFM_MERGE_FLEX(XFM_BF16, XFM_BF16, bf16_t, bf16_t)
+    XFM_MERGE_FLEX(XFM_F16, XFM_F16, f16_t, f16_t)
+    XFM_MERGE_FLEX(XFM_BF16, XFM_F32, bf16_t, float)
+    XFM_MERGE_FLEX(XFM_F16, XFM_F32, f16_t, float)
+#undef XFM_MERGE_FLEX
+    return XFM_EDTYPE;
 }
 }

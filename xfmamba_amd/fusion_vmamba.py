@@ -238,8 +238,12 @@ def _dwconv_act(conv: nn.Conv2d, act: nn.Module, x: torch.Tensor) -> torch.Tenso
     return act(conv(x))
 
 
-def _ss2d_core(x, x_proj_weight, dt_projs_weight, A_logs, Ds, dt_projs_bias, Cs_override=None, want_Cs=False, As=None):
+def _ss2d_core(x, x_proj_weight, dt_projs_weight, A_logs, Ds, dt_projs_bias, Cs_override=None, want_Cs=False, As=None,
+               scans=0):
     """x: (B, D, H, W) -> (y: (B, D, H*W) fp32, Cs in the layout of the active mode).
+
+    ``scans``: the route mode of forward_corev2 (fusion_vmamba.py:1052): 0 cross2d, 1 unidirectional, 2 bidirectional.
+    The fused kernels hard-wire the cross2d routes; the other modes run the operator chain.
 
     ``Cs_override`` lets the view streams of Cross_SS2Dv5 read their state through the fused
     stream's C (fusion_vmamba.py:537,568); ``want_Cs`` makes the call return its own C for that purpose
@@ -255,7 +259,7 @@ def _ss2d_core(x, x_proj_weight, dt_projs_weight, A_logs, Ds, dt_projs_bias, Cs_
     cd = x.dtype
     # short square maps (14 x 14 and below) in bf16: the channel-lane kernel -- dt_proj on MFMA inside the scan, one lane
     # per channel; no (B,4,D,L) step-size tensor, no cross_scan / cross_merge copies (csrc/ss2d_chan.hip)
-    if SS2D_MODE == "fused" and Cs_override is None and not want_Cs and chan_supported(x, H, W, N, K, D, R):
+    if scans == 0 and SS2D_MODE == "fused" and Cs_override is None and not want_Cs and chan_supported(x, H, W, N, K, D, R):
         return ss2d_chan_fn(x.reshape(B, D, L), x_proj_weight, dt_projs_weight, As, Dsf, bias, H, W), None
     # 7x7 maps (trunk stage 3, both fusion blocks): rows of 49 are too short for a parallel scan to pay; the
     # operator chain with the one-lane-per-row scan kernel is faster there and the (B,4,D,49) tensors are tiny.
@@ -263,7 +267,7 @@ def _ss2d_core(x, x_proj_weight, dt_projs_weight, A_logs, Ds, dt_projs_bias, Cs_
     #  kernel's LDS plan take the operator chain: the generic fused tile kernel measured 32.5 ms per block forward +
     #  backward at 96 x 96, the chain 14.1 ms)
     big_lean = N == 1 and cd in (torch.bfloat16, torch.float16) and 8704 < L <= 9216 and L % 8 == 0
-    if SS2D_MODE == "fused" and (64 < L <= 4096 or big_lean):
+    if scans == 0 and SS2D_MODE == "fused" and (64 < L <= 4096 or big_lean):
         # x_proj of all K routes as ONE dense GEMM on the map in natural order (route k's projection of
         # the permuted sequence is the permuted projection).  Routes 1/3 walk columns, so their slice of
         # the small x_dbl tensor is transposed to column-major here; dt_proj (batched GEMM) then emits
@@ -280,23 +284,26 @@ def _ss2d_core(x, x_proj_weight, dt_projs_weight, A_logs, Ds, dt_projs_bias, Cs_
         Cs = x_dbl[:, :, R + N:].contiguous() if Cs_override is None else Cs_override
         y = ss2d_core_fn(x.reshape(B, D, L), dts, As, Bs, Cs, Dsf, bias, H, W)
         return y, Cs
-    xs = cross_scan_fn(x, in_channel_first=True, out_channel_first=True, scans=0)           # (B, 4, D, L)
+    xs = cross_scan_fn(x, in_channel_first=True, out_channel_first=True, scans=scans)       # (B, 4, D, L)
     x_dbl = torch.matmul(x_proj_weight.to(cd), xs)                                          # (B, K, R+2N, L)
     dts, Bs, Cs = torch.split(x_dbl, [R, N, N], dim=2)
     dts = torch.matmul(dt_projs_weight.to(cd), dts).view(B, -1, L)
     Bs = Bs.contiguous()
     Cs = Cs.contiguous() if Cs_override is None else Cs_override
     ys = selective_scan_fn(xs.view(B, -1, L), dts, As, Bs, Cs, Dsf, bias, True, True, None)
-    y = cross_merge_fn(ys.view(B, K, -1, H, W), in_channel_first=True, out_channel_first=True, scans=0)
+    y = cross_merge_fn(ys.view(B, K, -1, H, W), in_channel_first=True, out_channel_first=True, scans=scans)
     return y, Cs
 
 
 _HIP_FORWARD_TYPES = ("v05", "v04", "v03", "v3")     # all: no fp32 up-cast, oflex output, cross2d routes
+# the same core on the unidirectional / bidirectional routes (fusion_vmamba.py:977-978, mode map :1052)
+_HIP_ROUTE_TYPES = {"v051d": 1, "v052d": 2}
 
 
 class SS2Dv2(nn.Module):
     """2-D selective scan block (fusion_vmamba.py:923-1254).  Built for the configurations the
-    reference reaches with ``forward_type="v05_noz"`` (and its ``_noz``-less sibling)."""
+    reference reaches with ``forward_type="v05_noz"`` (and its ``_noz``-less sibling), and for the
+    unidirectional / bidirectional route types ``v051d`` / ``v052d`` (``self.scans`` 1 / 2)."""
 
     def __init__(self, d_model=96, d_state=16, ssm_ratio=2.0, dt_rank="auto", act_layer=nn.SiLU,
                  d_conv=3, conv_bias=True, dropout=0.0, bias=False,
@@ -318,9 +325,11 @@ class SS2Dv2(nn.Module):
 
         self.disable_z, forward_type = cut("_noz", forward_type)
         self.disable_z_act, forward_type = cut("_nozact", forward_type)
-        if forward_type not in _HIP_FORWARD_TYPES:
-            raise NotImplementedError(f"forward_type {forward_type!r}: xfmamba_amd builds the cross2d/oflex core only "
-                                      f"({_HIP_FORWARD_TYPES}, optionally with _noz)")
+        if forward_type not in _HIP_FORWARD_TYPES and forward_type not in _HIP_ROUTE_TYPES:
+            raise NotImplementedError(f"forward_type {forward_type!r}: xfmamba_amd builds the oflex core on cross2d routes "
+                                      f"({_HIP_FORWARD_TYPES}) and on unidirectional / bidirectional routes "
+                                      f"({tuple(_HIP_ROUTE_TYPES)}), optionally with _noz / _nozact")
+        self.scans = _HIP_ROUTE_TYPES.get(forward_type, 0)
         self.out_norm = (LayerNorm2d if channel_first else nn.LayerNorm)(self.d_inner)
         self._As_pre = None          # A = -exp(A_logs) computed for all blocks of the trunk at once (transient)
 
@@ -344,7 +353,7 @@ class SS2Dv2(nn.Module):
     def forward_core(self, x: torch.Tensor):
         B, D, H, W = x.shape
         y, _ = _ss2d_core(x, self.x_proj_weight, self.dt_projs_weight, self.A_logs, self.Ds, self.dt_projs_bias,
-                          As=self._As_pre)
+                          As=self._As_pre, scans=self.scans)
         y = y.view(B, -1, H, W)
         if self.channel_first:
             return self.out_norm(y, out_dtype=x.dtype)          # LayerNorm2d kernel emits x's dtype directly
@@ -372,7 +381,7 @@ class SS2Dv2(nn.Module):
         B, H, W, C = h.shape
         L = H * W
         D, N, R = self.d_inner, self.d_state, self.dt_rank
-        if (TOKEN_SS2D and self.disable_z and SS2D_MODE == "fused" and self.with_dconv and isinstance(self.act, nn.SiLU)
+        if (TOKEN_SS2D and self.scans == 0 and self.disable_z and SS2D_MODE == "fused" and self.with_dconv and isinstance(self.act, nn.SiLU)
                 and isinstance(self.out_act, nn.Identity) and isinstance(self.out_norm, LayerNorm2d) and h.dtype == torch.bfloat16
                 and not _fp8.ENABLED and self.conv2d.kernel_size == (3, 3) and self.conv2d.padding == (1, 1)
                 and self.conv2d.groups == D and rows_supported(D) and chan_supported(h, H, W, N, 4, D, R)
@@ -396,7 +405,7 @@ class SS2Dv2(nn.Module):
         x = x.reshape(B, -1, H, W)
         x = _dwconv_act(self.conv2d, self.act, x) if self.with_dconv else self.act(x)
         D, N, R = x.shape[1], self.d_state, self.dt_rank
-        if (z is None and SS2D_MODE == "fused" and isinstance(self.out_act, nn.Identity) and isinstance(self.out_norm, LayerNorm2d)
+        if (z is None and self.scans == 0 and SS2D_MODE == "fused" and isinstance(self.out_act, nn.Identity) and isinstance(self.out_norm, LayerNorm2d)
                 and x.dtype == torch.bfloat16 and not _fp8.ENABLED and rows_supported(D) and chan_supported(x, H, W, N, 4, D, R)
                 and ytokens_supported(H, W, N)):
             # short maps (14 x 14, 7 x 7): the scan writes y TOKEN-MAJOR, so out_norm (the reference's channel-last nn.LayerNorm,
